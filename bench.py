@@ -36,7 +36,22 @@ clip step on one GPT-2 124M arena (fused vs torch foreach), and at G > 1 the
 weak-scaled DiLoCo step, 8 nodes per GPU (8G in total:
 diloco_8_nodes_per_gpu).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--no-extras]
+A plain run (`python bench.py --gpus N --steps K --warmup W`) does what the
+headline needs and no more: it builds the inputs, warms up, times the K outer
+steps and prints the result line; its "roofline" comes from the HIP events
+recorded around the timed steps' own launches.  Everything else above -- the
+CPU baseline, the rocprofv3 PMC passes, the queued / sustained kernel timings,
+the streaming-copy rate, the exchange timed alone, the extras -- runs only
+with --full (where --no-extras, --no-cpu-baseline and --no-pmc take legs out
+again); `--only LEG` runs that one leg in full detail.
+
+--dump-outputs DIR writes what the last timed step left its caller, right after
+the timed loop: a fixed, seeded sample of the positions of every node's
+parameters, the master and the outer momentum as DIR/<name>.npy (float32; the
+sampled positions as float64), under 64 MB in all.  The inputs are seeded, so
+with the same arguments two builds can be compared output for output.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full [--no-extras]] [--dump-outputs DIR]
        torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
 `python bench.py --gpus N` with N > 1 and no torchrun environment launches
 itself: this process runs the host legs (the CPU baseline) without touching
@@ -312,6 +327,37 @@ def xgmi_block(kind, nbytes, coll_ms, world, step_ms=None, what=None, latency_bo
     return out
 
 
+DUMP_BUDGET_BYTES = 56 << 20  # --dump-outputs: all files together, under the 64 MB a comparison may read
+
+
+def sample_positions(n, count, seed=20240607):
+    """`count` distinct positions of range(n), sorted: the same for every run and build."""
+    if count >= n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=count, replace=False))
+
+
+def dump_diloco_outputs(out_dir, eng, reps, n):
+    """What the outer step that just ran leaves its caller: every node's parameters
+    (reps[:, :n]), the master and the outer momentum (this rank's shard of the two when
+    they are sharded), each sampled at fixed positions."""
+    K = reps.shape[0]
+    count = DUMP_BUDGET_BYTES // (4 * K + 24)  # K + 2 fp32 values and two float64 positions per sample
+    os.makedirs(out_dir, exist_ok=True)
+    pos = sample_positions(n, count)
+    at = torch.from_numpy(pos).to(reps.device)
+    arrays = {"replicas_positions": pos.astype(np.float64),
+              "replicas": reps[:, :n].index_select(1, at).float().cpu().numpy()}
+    spos = sample_positions(eng.per, count)
+    sat = torch.from_numpy(spos).to(reps.device)
+    arrays["state_positions"] = spos.astype(np.float64)
+    arrays["master"] = eng.master.index_select(0, sat).float().cpu().numpy()
+    if eng.mom is not None:
+        arrays["momentum"] = eng.mom.index_select(0, sat).float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def bench_diloco(args, coll, dev):
     shapes = MODELS[args.model]()
     layout = ArenaLayout(shapes)
@@ -332,8 +378,11 @@ def bench_diloco(args, coll, dev):
     t = timed_loop(lambda: eng(reps), args.steps, args.warmup, coll)
     kern_single = timer.mean_ms()
     timer.on = False
+    if args.dump_outputs and coll.rank == 0:  # the last timed step's results, before anything else runs
+        dump_diloco_outputs(args.dump_outputs, eng, reps, n)
+    detail = args.detail and not args.pmc_child  # timings that take runs of their own (--full / --only)
     kern_ms, kern_how = kern_single, "HIP events around each launch"
-    if coll.world == 1 and not args.pmc_child:
+    if coll.world == 1 and detail:
         # one launch per step: time it queued back to back (what rocprofv3's kernel
         # durations measure; single-launch events add the host's launch gap)
         kern_ms = queued_ms(lambda: eng(reps), max(args.steps, 10), dev)
@@ -358,7 +407,7 @@ def bench_diloco(args, coll, dev):
     traffic, tnote = getattr(args, "pmc", None) or (None, "not measured (N > 1 or --no-pmc)")
     if coll.world > 1:
         traffic, tnote = None, "not measured at N > 1"
-    copy = None if args.pmc_child else stream_copy_rate(dev)
+    copy = stream_copy_rate(dev) if detail else None
     copy_sus = stream_copy_sustained(dev, 2 * SUSTAINED_LAUNCHES) if sus_ms else None
     args.copy_GBps = copy
     out = {
@@ -379,7 +428,7 @@ def bench_diloco(args, coll, dev):
             # master/momentum placement chosen by DiLoCoOuter._place (probe times per candidate)
             "placement": eng.placement},
     }
-    if coll.exchange:
+    if coll.exchange and detail:
         # the exchange alone: reduce-scatter + all-gather of the whole arena (the bytes of one
         # all-reduce), unchunked, no kernels; then the step's own bus rate beside it
         S = 4 * n
@@ -962,7 +1011,7 @@ def self_launch(args, argv):
     legs = {}
     t0 = time.perf_counter()
     cpu = None
-    if not args.no_cpu_baseline and args.only is None:
+    if args.full and not args.no_cpu_baseline and args.only is None:
         cpu = cpu_baseline_diloco(args.model, args.nodes)
     legs["cpu_baseline_s"] = round(time.perf_counter() - t0, 1)
     cmd = child_command(argv, args.gpus, free_port())
@@ -990,14 +1039,24 @@ def main():
                     help="simulated nodes in total (configs[2]: 8), spread nodes/N per GPU")
     ap.add_argument("--replicas", type=int, default=None,
                     help="simulated nodes per GPU (overrides --nodes / N; e.g. 8 for the weak-scaled form)")
-    ap.add_argument("--no-extras", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baseline, the rocprofv3 PMC traffic passes, the queued / "
+                         "sustained kernel timings, the streaming-copy rate, the exchange alone and the extras")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's results (sampled at fixed positions) as DIR/<name>.npy")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extras")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--only", default=None,
                     help="diloco|sparta|simple|demo|adamw or an extras name, e.g. sparta_k32_rows_torch_mask "
                          "(profiling runs)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC traffic passes")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 PMC traffic passes")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.only not in (None, "diloco"):
+        ap.error("--dump-outputs writes the headline (DiLoCo) step's results; not with --only " + args.only)
+    args.detail = args.full or args.only is not None
 
     if os.environ.get("GA_BENCH_WATCHDOG"):  # debugging aid: Python stacks on stderr every N s
         import faulthandler
@@ -1010,21 +1069,21 @@ def main():
     if args.pmc_child:  # a rocprofv3 PMC pass: the headline kernel only, a few launches
         coll = setup_dist(1)
         dev = torch.device("cuda", 0)
-        bench_diloco(argparse.Namespace(**{**vars(args), "steps": 3, "warmup": 1}), coll, dev)
+        bench_diloco(argparse.Namespace(**{**vars(args), "steps": 3, "warmup": 1, "dump_outputs": None}), coll, dev)
         return
     # host-side legs first, while this process has not touched the GPU (the
     # children are started by fork+exec; none of them runs in a GPU-initialised process)
     cpu = None
     legs = {}
     t0 = time.perf_counter()
-    if rank0 and not args.no_cpu_baseline and args.only is None:
+    if rank0 and args.full and not args.no_cpu_baseline and args.only is None:
         # at N > 1 under torchrun the other ranks wait in the rendezvous meanwhile; the
         # baseline is the reference's configs[2] job (8 gloo node processes) on this host
         cpu = cpu_baseline_diloco(args.model, args.nodes)
     legs["cpu_baseline_s"] = round(time.perf_counter() - t0, 1)
-    args.pmc = (None, "not measured (N > 1 or --no-pmc)")
+    args.pmc = (None, "not measured (N > 1 or --no-pmc)" if args.full else "not measured (needs --full)")
     t0 = time.perf_counter()
-    if single and not args.no_pmc and args.only is None and not under_profiler():
+    if single and args.full and not args.no_pmc and args.only is None and not under_profiler():
         args.pmc = pmc_traffic_live(args)
     legs["pmc_passes_s"] = round(time.perf_counter() - t0, 1)
 
@@ -1053,14 +1112,14 @@ def main():
 
     head = bench_diloco(args, coll, dev)
     extras = {}
-    if not args.no_extras and args.only != "diloco":
+    if args.full and not args.no_extras and args.only != "diloco":
         runs = list(extra_runs)
         if coll.world == 1:
             runs.insert(0, ("diloco_torch_per_tensor_gpu",
                             lambda a, c, d: bench_diloco_torch_gpu(a, c, d, head["ms_per_step"])))
         if coll.world > 1:  # the weak-scaled form: 8 nodes on every GPU (8N in total)
             def diloco_weak(a, c, d):
-                r = bench_diloco(argparse.Namespace(**{**vars(a), "replicas": 8}), c, d)
+                r = bench_diloco(argparse.Namespace(**{**vars(a), "replicas": 8, "dump_outputs": None}), c, d)
                 for key in ("ms_per_step", "value", "kernel_ms"):
                     r[key] = round(r[key], 4)
                 r["scaling"] = "weak"
@@ -1089,6 +1148,7 @@ def main():
         "n_gpus": coll.world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(head["ms_per_step"], 4),
         "higher_is_better": True,
         "scaling": "strong",

@@ -36,8 +36,10 @@ def test_abi_checks_under_asan(tmp_path):
     r = subprocess.run([sys.executable, "-c", probe], env=env, capture_output=True, text=True, timeout=300,
                        cwd=str(tmp_path))
     assert r.returncode == 0 and "asan-active" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    # --rootdir: with no settings file pytest would take the common ancestor of the working
+    # directory and the test file as its root and scan it, a directory this user may not read
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_abi.py"), "-q",
-                        "-p", "no:cacheprovider"], env=env, capture_output=True, text=True, timeout=600,
-                       cwd=str(tmp_path))
+                        "-p", "no:cacheprovider", "--rootdir", ROOT], env=env, capture_output=True, text=True,
+                       timeout=600, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "AddressSanitizer" not in r.stderr

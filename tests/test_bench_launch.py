@@ -1,6 +1,7 @@
 """bench.py's self-launch path (`python bench.py --gpus N`, N > 1, no torchrun):
 the parent builds the torch.distributed.run command, never touches the GPU, and
-forwards rank 0's JSON line with its CPU baseline merged in.  CPU only."""
+forwards rank 0's JSON line with its CPU baseline merged in (with --full), and
+the --dump-outputs writer.  CPU only, but for the dump of a real step."""
 import json
 import os
 import sys
@@ -57,8 +58,8 @@ def test_main_self_launches_without_torchrun_env(monkeypatch):
 
 
 def test_self_launch_forwards_the_child_line(monkeypatch, capsys):
-    """self_launch with the child replaced by a stub that prints a rank-0 line:
-    one JSON line on stdout, CPU baseline merged, child's exit code returned."""
+    """self_launch of a --full run with the child replaced by a stub that prints a
+    rank-0 line: one JSON line on stdout, CPU baseline merged, child's exit code returned."""
     import subprocess
     import types
     calls = {}
@@ -69,14 +70,75 @@ def test_self_launch_forwards_the_child_line(monkeypatch, capsys):
 
     monkeypatch.setattr(subprocess, "run", fake_run)
     monkeypatch.setattr(bench, "cpu_baseline_diloco", lambda model, K: {"value": 1.0, "cores": 2})
-    args = bench.argparse.Namespace(gpus=2, no_cpu_baseline=False, only=None, model="gpt2-124m", nodes=8, replicas=None)
-    assert bench.self_launch(args, ["--gpus", "2"]) == 0
+    args = bench.argparse.Namespace(gpus=2, full=True, no_cpu_baseline=False, only=None, model="gpt2-124m", nodes=8,
+                                    replicas=None)
+    assert bench.self_launch(args, ["--gpus", "2", "--full"]) == 0
     out = capsys.readouterr().out.strip().splitlines()
     assert len(out) == 1
     line = json.loads(out[0])
     assert line["n_gpus"] == 2 and line["cpu_baseline"] == {"value": 1.0, "cores": 2}
     assert "--nproc-per-node=2" in calls["cmd"]
     assert calls["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_plain_self_launch_skips_the_cpu_baseline(monkeypatch, capsys):
+    """Without --full the parent times no CPU baseline: the child's line goes out as it is."""
+    import subprocess
+    import types
+
+    def fake_run(cmd, env=None, stdout=None, text=None):
+        return types.SimpleNamespace(returncode=0, stdout=json.dumps({"metric": "m", "n_gpus": 2}) + "\n")
+
+    def no_baseline(model, K):
+        raise AssertionError("a plain run timed the CPU baseline")
+
+    monkeypatch.setattr(subprocess, "run", fake_run)
+    monkeypatch.setattr(bench, "cpu_baseline_diloco", no_baseline)
+    args = bench.argparse.Namespace(gpus=2, full=False, no_cpu_baseline=False, only=None, model="gpt2-124m", nodes=8,
+                                    replicas=None)
+    assert bench.self_launch(args, ["--gpus", "2"]) == 0
+    assert json.loads(capsys.readouterr().out.strip())["cpu_baseline"] is None
+
+
+def test_dump_sample_is_fixed_and_within_budget():
+    """--dump-outputs samples the same sorted, distinct positions every run, and at
+    the headline's K = 8 all its files together stay under 64 MB."""
+    a, b = bench.sample_positions(1000003, 4096), bench.sample_positions(1000003, 4096)
+    assert (a == b).all() and (a[1:] > a[:-1]).all() and 0 <= a[0] and a[-1] < 1000003
+    assert (bench.sample_positions(100, 4096) == range(100)).all()
+    K = 8
+    count = bench.DUMP_BUDGET_BYTES // (4 * K + 24)
+    assert count * (4 * (K + 2) + 2 * 8) + 5 * 128 <= 64 * 10 ** 6
+
+
+@pytest.mark.gpu
+def test_dump_writes_the_steps_results_at_the_sampled_positions(tmp_path, monkeypatch):
+    """dump_diloco_outputs after one outer step of 3 nodes x 5003 elements, the budget
+    cut to 1000 samples: float32 / float64 files holding exactly the replicas', the
+    master's and the momentum's values at the recorded positions."""
+    import numpy as np
+    import torch
+    from gym_amd.comm import Collective
+    from gym_amd.engine import DiLoCoOuter
+    K, n = 3, 5003
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(11)
+    reps = (torch.randn(K, n, generator=g) * 0.02).to(dev)
+    eng = DiLoCoOuter(Collective(), K, n, dev, torch.float32)
+    eng.init_master(reps[0].clone())
+    eng(reps)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1000 * (4 * K + 24))
+    bench.dump_diloco_outputs(str(tmp_path / "out"), eng, reps, n)
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert sorted(got) == ["master", "momentum", "replicas", "replicas_positions", "state_positions"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    pos = got["replicas_positions"].astype(np.int64)
+    assert pos.shape == (1000,) and np.array_equal(pos, bench.sample_positions(n, 1000))
+    assert np.array_equal(got["state_positions"], got["replicas_positions"])
+    assert np.array_equal(got["replicas"], reps.cpu().numpy()[:, pos])
+    assert np.array_equal(got["master"], eng.master.cpu().numpy()[pos])
+    assert np.array_equal(got["momentum"], eng.mom.cpu().numpy()[pos])
+    assert np.array_equal(got["replicas"][1], got["replicas"][0])  # every node holds the new master
 
 
 @pytest.mark.parametrize("world,per_gpu", [(1, 8), (2, 4), (4, 2), (8, 1)])
