@@ -32,7 +32,7 @@ __global__ __launch_bounds__(kOptBlock) void adam_kernel(float* __restrict__ par
     m_ += rep * ld;
     v_ += rep * ld;
     const float coef = clip_coef ? clip_coef[2 * rep] : 1.f;
-    const bool scale = coef < 1.f;
+    const bool scale = !(coef >= 1.f);  // a NaN coefficient scales too (clamp(nan, max=1) is nan)
     const int64_t nv = n >> 2;
     const int64_t lo = (int64_t)blockIdx.x * kOptChunk;
     const int64_t hi = lo + kOptChunk < nv ? lo + kOptChunk : nv;
@@ -127,8 +127,9 @@ __global__ __launch_bounds__(kOptBlock) void sumsq_kernel(const T* __restrict__ 
     if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// out[0] = min(1, max_norm / (sqrt(sum partials) + 1e-6)), out[1] = the total norm
-// (torch.nn.utils.clip_grad_norm_ with norm_type 2)
+// out[0] = clamp(max_norm / (sqrt(sum partials) + 1e-6), max=1), out[1] = the total norm
+// (torch.nn.utils.clip_grad_norm_ with norm_type 2; NaN norm -> NaN coefficient,
+// infinite norm -> 0)
 __global__ __launch_bounds__(kOptBlock) void clip_coef_kernel(const float* __restrict__ partials, int np,
                                                               float max_norm, float* __restrict__ out) {
     __shared__ float red[kOptBlock / 64];
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(kOptBlock) void clip_coef_kernel(const float* __res
     if (threadIdx.x == 0) {
         const float total = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
         const float c = max_norm / (total + 1e-6f);
-        out[0] = c < 1.f ? c : 1.f;
+        out[0] = c >= 1.f ? 1.f : c;  // torch's clamp(c, max=1): a NaN norm gives a NaN coefficient
         out[1] = total;
     }
 }

@@ -451,8 +451,9 @@ def sumsq_partials(device, K=1):
 
 
 def grad_clip_coef(grad, n, max_norm, partials, out):
-    """Per replica k of grad ([K, ld] set or 1-D): out[2k] <- min(1, max_norm /
-    (||grad_k[:n]||_2 + 1e-6)), out[2k+1] <- the norm (device side)."""
+    """Per replica k of grad ([K, ld] set or 1-D): out[2k] <- clamp(max_norm /
+    (||grad_k[:n]||_2 + 1e-6), max=1) (NaN for a NaN norm, as torch's clamp),
+    out[2k+1] <- the norm (device side)."""
     g2 = _as2d(grad)
     _gpu(g2, partials, out)
     K, ld = _rows_ld(g2)

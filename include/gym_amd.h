@@ -427,7 +427,8 @@ GA_API int ga_sumsq_partials_count(void);
  * Gradient-norm clipping coefficient per replica k < K of a gradient replica set
  * (replica k: n elements at grad + k*ld):
  *   out[2k+1] = ||grad_k||_2 (fp32 partial sums in a fixed order), and
- *   out[2k]   = min(1, max_norm / (out[2k+1] + 1e-6)).
+ *   out[2k]   = clamp(max_norm / (out[2k+1] + 1e-6), max = 1) as torch clamps:
+ *               a NaN norm gives a NaN coefficient (never 1), an infinite norm 0.
  * `partials` holds K * ga_sumsq_partials_count() floats.  Device side only
  * (nothing synchronises); ga_adam_step applies out[2k] to replica k.
  * Replaces: torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) at
@@ -442,7 +443,9 @@ GA_API int ga_grad_clip_coef(int dtype, const void* grad, int64_t K, int64_t ld,
  * exp_avg, exp_avg_sq: [K, ld] sets, n elements per replica, 16-byte aligned),
  * every replica with the same hyper-parameters, in torch's op order
  * (torch/optim/adam.py, _multi_tensor_adam):
- *   g = grad * clip_coef[2k]  (and written back) if clip_coef != null and < 1
+ *   g = grad * clip_coef[2k]  (and written back) if clip_coef != null and !(clip_coef[2k] >= 1):
+ *                             a NaN coefficient scales too, so the replica's gradient, moments
+ *                             and parameters become NaN as after clip_grad_norm_ + step()
  *   p *= wd_factor            (AdamW: 1 - lr*weight_decay, computed by the caller in double)
  *   g += l2_wd * p            (Adam with weight_decay)
  *   m = lerp(m, g, lerp_w)    (lerp_w = 1 - beta1)

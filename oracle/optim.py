@@ -21,19 +21,28 @@ def _fma(a, b, c):
 
 
 def clip_coef(grads, max_norm):
-    """(coef, total_norm) of clip_grad_norm_ (norm type 2, eps 1e-6, clamped to 1)."""
-    total = np.sqrt(sum(float(np.sum(np.asarray(g, np.float64) ** 2)) for g in grads))
-    coef = min(1.0, float(f32(max_norm) / (f32(total) + f32(1e-6))))
-    return coef, total
+    """(coef, total_norm) of clip_grad_norm_ (norm type 2, eps 1e-6, clamped to 1
+    as torch.clamp(max=1) does: a NaN norm gives a NaN coefficient, an infinite one 0)."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        total = np.sqrt(sum(float(np.sum(np.asarray(g, np.float64) ** 2)) for g in grads))
+        coef = float(f32(max_norm) / (f32(total) + f32(1e-6)))
+    return (1.0 if coef >= 1.0 else coef), total
 
 
 def adam_step(p, g, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, decoupled=True,
               clip=None):
     """One Adam(W) step on fp32 arrays; step = the step count after increment.
+    `clip` is clip_coef's coefficient: the gradient is scaled unless clip >= 1, so
+    a NaN coefficient makes the whole step NaN, as clip_grad_norm_ does.
     Returns (p, g_used, m, v)."""
+    with np.errstate(over="ignore", invalid="ignore"):  # non-finite gradients are part of the contract
+        return _adam_step(p, g, m, v, step, lr, betas, eps, weight_decay, decoupled, clip)
+
+
+def _adam_step(p, g, m, v, step, lr, betas, eps, weight_decay, decoupled, clip):
     b1, b2 = betas
     p, g, m, v = (np.asarray(x, f32).copy() for x in (p, g, m, v))
-    if clip is not None and clip < 1.0:
+    if clip is not None and not clip >= 1.0:
         g = (g * f32(clip)).astype(f32)
     if weight_decay != 0:
         if decoupled:
@@ -41,7 +50,11 @@ def adam_step(p, g, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_de
         else:
             g = _fma(f32(weight_decay), p, g)
     w = f32(1 - b1)
-    m = _fma(w, (g - m).astype(f32), m)  # lerp, weight < 0.5
+    d = (g - m).astype(f32)
+    if w < 0.5:  # ATen's lerp: a + w*(b-a) for w < 0.5, else b - (b-a)*(1-w), each rounded once
+        m = _fma(w, d, m)
+    else:
+        m = _fma(-d, f32(1) - w, g)
     v = (v * f32(b2)).astype(f32)
     v = _fma((f32(1 - b2) * g).astype(f32), g, v)
     bc1 = 1 - b1 ** step

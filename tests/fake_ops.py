@@ -188,14 +188,18 @@ def _adam_one(param, grad, exp_avg, exp_avg_sq, lerp_w, beta2, one_m_beta2, eps,
               bc2_sqrt, coef):
     f = np.float32
     p, g, m, v = _np(param).copy(), _np(grad).copy(), _np(exp_avg).copy(), _np(exp_avg_sq).copy()
-    if coef is not None and coef < 1.0:
+    if coef is not None and not coef >= 1.0:  # a NaN coefficient scales too (ga_adam_step's rule)
         g = (g * f(coef)).astype(f)
         grad.copy_(torch.from_numpy(g))
     if wd_factor != 1.0:
         p = (p * f(wd_factor)).astype(f)
     if l2_wd != 0.0:
         g = (g.astype(np.float64) + float(f(l2_wd)) * p.astype(np.float64)).astype(f)
-    m = (m.astype(np.float64) + float(f(lerp_w)) * (g - m).astype(f).astype(np.float64)).astype(f)
+    d = (g - m).astype(f).astype(np.float64)
+    if f(lerp_w) < 0.5:
+        m = (m.astype(np.float64) + float(f(lerp_w)) * d).astype(f)
+    else:
+        m = (g.astype(np.float64) - d * float(f(1) - f(lerp_w))).astype(f)
     v = (v * f(beta2)).astype(f)
     v = (v.astype(np.float64) + (f(one_m_beta2) * g).astype(f).astype(np.float64) * g).astype(f)
     denom = ((np.sqrt(v).astype(f) / f(bc2_sqrt)).astype(f) + f(eps)).astype(f)

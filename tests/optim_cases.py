@@ -52,6 +52,8 @@ CASES = [
     ("adamw-clip", torch.optim.AdamW, {"lr": 1e-3}, 0.5, None),
     ("adam-l2", torch.optim.Adam, {"lr": 2e-3, "weight_decay": 0.05}, None, None),
     ("adamw-unused-param", torch.optim.AdamW, {"lr": 1e-3}, None, 1),
+    ("adamw-beta1-small", torch.optim.AdamW, {"lr": 1e-3, "betas": (0.3, 0.9)}, None, None),  # lerp weight >= 0.5
+    ("adamw-clip-unused-param", torch.optim.AdamW, {"lr": 1e-3}, 0.5, 1),
 ]
 
 
