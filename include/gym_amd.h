@@ -342,6 +342,23 @@ typedef struct ga_demo_tensor {
 GA_API int ga_demo_tensor_bytes(void);
 
 /*
+ * Alignment, for the four DeMo entry points below (ga_demo_encode,
+ * ga_demo_encode_sym, ga_demo_decode, ga_demo_decode_sym): param, grad and delta
+ * may have any element alignment and any ld; the results are bit-identical
+ * either way and nothing outside the rows is written.  The kernels use 4-element
+ * vector accesses only when every arena base passed is 16 B (fp32) / 8 B (bf16)
+ * aligned and, for K > 1, ld % 4 == 0 (per tensor also offset % 4 == 0 and
+ * cols % 4 == 0, which an arena layout aligned to 64 elements gives); otherwise
+ * they load and store element by element, which is slower.  The payload needs
+ * only its natural 4 B alignment; payload_stride may be any value >= 2*M.
+ *
+ * Payload indices on decode: an entry whose index is outside the chunk's
+ * coefficient range [0, n1*n2) -- negative or too large -- is ignored: it adds
+ * neither its value nor a hit to any coefficient's mean.  (The encoders emit
+ * only valid indices; a receiver does not have to validate gathered payloads.)
+ */
+
+/*
  * Encode + compress + residual for every chunk of every tensor, for each of
  * K replicas (replica r: param/grad/delta at + r*ld, payload at + r*payload_stride):
  *   p     *= wd_factor                      if wd_factor != 1 (demo.py:159-160; the

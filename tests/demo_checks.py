@@ -151,3 +151,73 @@ class Bf16Agreement:
         frac = self.agree / max(self.total, 1)
         assert frac >= self.min_all, f"overall bf16 sign agreement {frac:.4f} < {self.min_all}"
         return frac, self.worst
+
+
+# ---- exact-tie model of the encode's top-k (test infrastructure) -------------
+# A 64x64 chunk that is zero except v = 2^-3 at (i, i) makes every MFMA chain of
+# Y = F^T X F a single non-zero term, so the kernels' coefficient is exactly
+# fl32(F32[i][b] * F32[i][d]) * v: an integer model predicts the payload to the bit.
+TIE_V = 0.125
+KCAND = 128  # demo_wave.hip kCand: the wave kernel's fast-path candidate capacity
+
+
+def tie_chunk_coeffs(F32, i, v=TIE_V):
+    """fp32 [64, 64] coefficients (b, d) of the chunk with v at (i, i); F32 the
+    plan's fp32 64-point table F[i][k]."""
+    f = np.asarray(F32, np.float32)[i]
+    return (f[:, None] * f[None, :]) * np.float32(v)  # one fp32 rounding; * 2^-3 is exact
+
+
+def keys_of(y):
+    """The kernels' selection key: (bits & 0x7fffffff) + 1 (magnitude order, > 0)."""
+    return (np.ascontiguousarray(y, np.float32).view(np.uint32).astype(np.int64) & 0x7FFFFFFF) + 1
+
+
+def topk_by_key(y, k):
+    """Top k of the flattened y by key, ties to the lowest index, entries in
+    ascending index: (idx int64[k], value bits uint32[k], tie multiplicity of the
+    k-th key, how many of the tied are needed)."""
+    flat = np.ascontiguousarray(y, np.float32).reshape(-1)
+    key = keys_of(flat)
+    order = np.argsort(-key, kind="stable")[:k]
+    idx = np.sort(order)
+    kth = key[order[-1]]
+    return idx, flat.view(np.uint32)[idx], int((key == kth).sum()), int(k - (key > kth).sum())
+
+
+def wave_candidate_count(y, k):
+    """How many coefficients the wave kernel's fast path would list
+    (demo_wave.hip chunk64_tail): lane (l, h) holds b = 2 (r%4 + 8 (r//4) + 4 h) + par,
+    d = 2 l + qc; T0 = the largest 12-bit key prefix (bits 30..19) that at least k
+    lane maxima reach (at least 1); the count of keys >= T0.  Above KCAND the
+    kernel takes its all-keys fallback."""
+    key = keys_of(y).reshape(64, 64)
+    r = np.arange(16)
+    lane_max = np.empty((2, 32), np.int64)
+    for h in range(2):
+        rows = (2 * ((r & 3) + 8 * (r >> 2) + 4 * h)[:, None] + np.arange(2)[None, :]).reshape(-1)
+        for l in range(32):
+            lane_max[h, l] = key[np.ix_(rows, [2 * l, 2 * l + 1])].max()
+    T0 = 0
+    for bit in range(30, 18, -1):
+        cnd = T0 | (1 << bit)
+        if (lane_max >= cnd).sum() >= k:
+            T0 = cnd
+    T0 = max(T0, 1)
+    return int((key >= T0).sum())
+
+
+def scatter_mean_valid(idx, val, n1, n2):
+    """oracle.demo.scatter_mean over sources idx/val [S, gy, gx, k] with the entries
+    whose index is outside [0, n1*n2) dropped (the decoders ignore them)."""
+    idx = np.asarray(idx, np.int64)
+    val = np.asarray(val, np.float64)
+    S, gy, gx, k = idx.shape
+    nv = n1 * n2
+    ok = (idx >= 0) & (idx < nv)
+    rows = np.broadcast_to(np.arange(gy * gx).reshape(1, gy, gx, 1), idx.shape)
+    s = np.zeros((gy * gx, nv))
+    c = np.zeros((gy * gx, nv))
+    np.add.at(s, (rows[ok], idx[ok]), val[ok])
+    np.add.at(c, (rows[ok], idx[ok]), 1.0)
+    return np.where(c > 0, s / np.maximum(c, 1.0), 0.0).reshape(gy, gx, n1, n2), c.reshape(gy, gx, nv)
