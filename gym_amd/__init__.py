@@ -16,7 +16,10 @@ def __getattr__(name):
     if name in ("Trainer", "LocalTrainer"):
         from . import trainer
         return getattr(trainer, name)
+    if name == "NodeDrift":
+        from .metrics import NodeDrift
+        return NodeDrift
     raise AttributeError(name)
 
 
-__all__ = ["TrainNode", "Trainer", "LocalTrainer"]
+__all__ = ["TrainNode", "Trainer", "LocalTrainer", "NodeDrift"]

@@ -74,6 +74,41 @@ def replica_mean(src, dst, n=None, divisor=None, rows=None):
                                 _stream()), "ga_replica_mean")
 
 
+GRAM_MAX_K = 32  # ga_replica_gram: the 32x32 MFMA tile
+
+
+def replica_gram_chain():
+    """L of ga_replica_gram's error bound (include/gym_amd.h)."""
+    return int(lib().ga_replica_gram_chain())
+
+
+def replica_gram(src, n=None, want_dist=True):
+    """(gram [K, K], rowsum [K], dist2 [K] or None) of the first n elements of the
+    rows of a replica set [K, ld] (or one 1-D replica), float64 on src's device:
+    gram[i, j] = x_i . x_j, rowsum[k] = sum x_k, dist2[k] = |x_k - mean_k x_k|^2
+    (ga_replica_gram, one read of src; K <= 32)."""
+    src2 = _as2d(src)
+    _gpu(src2)
+    K, ld = _rows_ld(src2)
+    if src2.stride(1) != 1:
+        raise ValueError("replica_gram: rows must be contiguous")
+    n = src2.shape[1] if n is None else int(n)
+    if n < 0 or n > src2.shape[1]:
+        raise ValueError("replica_gram: n exceeds the row length")
+    code = _dtype_code(src2)
+    nbytes = int(lib().ga_replica_gram_workspace_bytes(K, n))
+    if nbytes < 0:
+        raise ValueError(f"replica_gram: {K} replicas, at most {GRAM_MAX_K} are supported")
+    dev = src2.device
+    gram = torch.empty(K, K, dtype=torch.float64, device=dev)
+    rowsum = torch.empty(K, dtype=torch.float64, device=dev)
+    dist2 = torch.empty(K, dtype=torch.float64, device=dev) if want_dist else None
+    work = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
+    check(lib().ga_replica_gram(code, _p(src2), K, ld, n, _p(gram), _p(rowsum), _p(dist2), _p(work), _stream()),
+          "ga_replica_gram")
+    return gram, rowsum, dist2
+
+
 def diloco_outer(src, master, mom, dst, n, divisor, lr, momentum, dampening, weight_decay, nesterov,
                  first_step):
     """Fused DiLoCo outer step over [0, n) of master/mom (see include/gym_amd.h)."""

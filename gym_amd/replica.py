@@ -544,7 +544,8 @@ class ReplicaTrainNode:
 
     def __init__(self, model, train_dataset, val_dataset, strategy, device, rank, num_nodes, K, num_epochs,
                  max_steps=None, batch_size=16, minibatch_size=16, val_size=64, val_interval=100, shuffle=True,
-                 autocast=False, replica_forward="loop", replica_vmap_chunk=None, **kwargs):
+                 autocast=False, replica_forward="loop", replica_vmap_chunk=None, correlation_interval=None,
+                 **kwargs):
         from .train_node import RunLog
         seed = kwargs.get("seed", 42)
         torch.manual_seed(seed)
@@ -582,6 +583,8 @@ class ReplicaTrainNode:
         strategy.max_steps = max_steps
         self.local_step = 0
         self.logger = RunLog(strategy, max_steps) if rank == 0 else None
+        self.correlation_interval = correlation_interval
+        self.drift = None  # NodeDrift, built at the first measurement (correlation_interval set)
 
     def _next(self, k):
         try:
@@ -660,6 +663,20 @@ class ReplicaTrainNode:
                     p.copy_(v)
             self.logger.log_loss(loss=self._eval_loss(clone), name="global")
 
+    def _node_drift(self):
+        """Model correlation and consensus distance over all num_nodes nodes
+        (train_node.py:498-573 through ga_replica_gram on the replica arena):
+        every process calls it, the first records the two numbers."""
+        from .metrics import NodeDrift
+        ra = self.runner.ra
+        if self.drift is None:
+            self.drift = NodeDrift(self.runner.coll, self.K, ra.ld, ra.ld, ra.layout.n_params, ra.device, ra.dtype)
+        out = self.drift(ra.flat_set)
+        if out is not None and self.logger is not None:
+            self.logger.log_metric("avg_model_correlation", out["avg_model_correlation"])
+            self.logger.log_metric("consensus_distance", out["consensus_distance"])
+        return out
+
     def train(self):
         world = self.runner.coll.world
         while self.local_step < self.max_steps:
@@ -669,6 +686,8 @@ class ReplicaTrainNode:
             self.local_step += 1
             if self.logger is not None:
                 self.logger.increment_step()
+            if self.correlation_interval and self.local_step % self.correlation_interval == 0:
+                self._node_drift()  # the condition of train_node.py:615
             if world > 1:
                 dist.barrier()
         if hasattr(self.runner, "sparta"):

@@ -9,7 +9,9 @@ local model, rank 1 the node-averaged model), a barrier every step.
 
 MI355X changes: the initial broadcast and the evaluation average run over the
 strategy's flat parameter arena (one collective + one ga_replica_mean launch
-instead of one per tensor).  Logging is a small in-memory recorder (the
+instead of one per tensor); the model-correlation metric the reference disables
+(train_node.py:498-573) runs on the arena every `correlation_interval` steps
+(gym_amd.metrics.NodeDrift; off by default).  Logging is a small in-memory recorder (the
 reference's wandb/CSV loggers and its disabled checkpointing are out of scope).
 """
 import copy
@@ -35,6 +37,7 @@ class RunLog:
         self.train = []
         self.evals = []
         self.lrs = []
+        self.metrics = []
         strategy.lr_callbacks.append(self.log_lr)
 
     def log_train(self, loss):
@@ -46,12 +49,16 @@ class RunLog:
     def log_lr(self, lr):
         self.lrs.append((self.step, float(lr)))
 
+    def log_metric(self, name, value):
+        self.metrics.append((self.step, name, float(value)))
+
     def increment_step(self):
         self.step += 1
 
     def summary(self):
         """Plain lists (picklable through the trainer's result queue)."""
-        return {"train": list(self.train), "evals": list(self.evals), "lrs": list(self.lrs)}
+        return {"train": list(self.train), "evals": list(self.evals), "lrs": list(self.lrs),
+                "metrics": list(self.metrics)}
 
 
 class TrainNode(LogModule):
@@ -61,7 +68,8 @@ class TrainNode(LogModule):
                  val_dataset: Union[torch.utils.data.Dataset, Callable[[int, int, bool], torch.utils.data.Dataset]],
                  strategy: Strategy, device: torch.device, rank: int, num_nodes: int, num_epochs: int,
                  max_steps: int = None, batch_size: int = 16, minibatch_size: int = 16, val_size: int = 64,
-                 val_interval: int = 100, checkpoint_interval: int = 100, autocast: bool = False, **kwargs):
+                 val_interval: int = 100, checkpoint_interval: int = 100, autocast: bool = False,
+                 correlation_interval: int = None, **kwargs):
         seed = kwargs.get("seed", 42)
         torch.manual_seed(seed)
         torch.cuda.manual_seed(seed)
@@ -86,6 +94,7 @@ class TrainNode(LogModule):
         self.val_interval = val_interval
         self.autocast = autocast
         self.checkpoint_interval = checkpoint_interval
+        self.correlation_interval = correlation_interval
         self.kwargs = kwargs
         self.build_dataloaders()
         torch.manual_seed(42)
@@ -100,6 +109,7 @@ class TrainNode(LogModule):
         self.local_step = 0
         self.epoch = 0
         self.logger = None
+        self.drift = None  # NodeDrift, built at the first measurement (correlation_interval set)
 
     def build_dataloaders(self):
         self.train_dataloader = DataLoader(self.train_dataset, batch_size=self.minibatch_size,
@@ -193,6 +203,26 @@ class TrainNode(LogModule):
             if self.rank == 0 and self.logger is not None:
                 self.logger.log_loss(loss=g.item(), name="global")
 
+    def _node_drift(self):
+        """Model correlation and consensus distance over the nodes
+        (train_node.py:498-573 through ga_replica_gram): every rank calls it,
+        rank 0 records the two numbers.  The vector is the strategy's parameter
+        arena, or a flat copy of model.parameters() for a strategy without one."""
+        from .comm import Collective
+        from .metrics import NodeDrift, flat_parameters
+        arena = getattr(self.strategy, "arena", None)
+        if arena is not None:
+            flat, n_true = arena.flat, arena.layout.n_params
+        else:
+            flat, n_true = flat_parameters(self.model)
+        if self.drift is None:
+            self.drift = NodeDrift(Collective(), 1, flat.numel(), flat.numel(), n_true, flat.device, flat.dtype)
+        out = self.drift(flat)
+        if out is not None and self.rank == 0 and self.logger is not None:
+            self.logger.log_metric("avg_model_correlation", out["avg_model_correlation"])
+            self.logger.log_metric("consensus_distance", out["consensus_distance"])
+        return out
+
     def train(self):
         if self.max_steps is None:
             self.max_steps = self.num_epochs * len(self.train_dataloader) / (self.batch_size // self.minibatch_size)
@@ -206,6 +236,8 @@ class TrainNode(LogModule):
             self.local_step += 1
             if self.rank == 0:
                 self.logger.increment_step()
+            if self.correlation_interval and self.local_step % self.correlation_interval == 0:
+                self._node_drift()  # the condition of train_node.py:615
             if self.num_nodes > 1:
                 dist.barrier()
         self.strategy.finish()

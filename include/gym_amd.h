@@ -477,6 +477,42 @@ GA_API int ga_adam_step(int dtype, void* param, void* grad, float* exp_avg, floa
                         float wd_factor, float l2_wd, float step_size, float bc2_sqrt, const float* clip_coef,
                         hipStream_t stream);
 
+/* ---- node drift: model correlation and consensus distance ---------------- */
+
+/* Bytes of the `work` buffer ga_replica_gram needs for K replicas of n elements
+ * (one fp32 partial of K*K + 2K values per workgroup); -1 for K outside 1..32 or n < 0. */
+GA_API int64_t ga_replica_gram_workspace_bytes(int64_t K, int64_t n);
+
+/* L: the most fused multiply-adds any fp32 accumulator of ga_replica_gram takes
+ * before it is written out as a partial (<= 4096).  The fp32 error of a Gram entry
+ * is first-order bounded by (L + 16) * 2^-24 * sum_e |x_i[e] x_j[e]|. */
+GA_API int ga_replica_gram_chain(void);
+
+/*
+ * One read of a replica set src [K, ld] (K <= 32, n elements per row, f32 or bf16
+ * widened to f32) gives, in fp64 on the device:
+ *   gram[i*K + j] = sum_e x_i[e] * x_j[e]          (the full symmetric K x K matrix)
+ *   rowsum[k]     = sum_e x_k[e]
+ *   dist2[k]      = sum_e (x_k[e] - m[e])^2, m[e] = (fp32 sum of x_k[e] in ascending k) / K
+ *                   with a true division (ga_replica_mean's rule); skipped if dist2 is null.
+ * From gram and rowsum the host derives every pair's Pearson correlation; dist2 is
+ * the squared distance of each node to the node mean (the consensus distance),
+ * computed from centred values because gram_kk - 2 x_k.m + m.m cancels when the
+ * nodes are close.  The Gram products run on the f32 MFMA (K <= 16: 16x16x4,
+ * else 32x32x2, rows >= K fed zeros), fp32 partials per workgroup go to `work`
+ * (ga_replica_gram_workspace_bytes) and a second kernel sums them in a fixed order
+ * in fp64: no atomics, the same input gives the same bits.  Elements at index >= n
+ * of a row (tail and ld - n padding) are never read.  16-byte vector loads (8-byte
+ * for bf16) when src is so aligned and ld % 4 == 0, element loads otherwise, same
+ * results.  n == 0 zeroes the (non-null) outputs.  K > 32: GA_EUNSUP.
+ *
+ * Replaces: exogym/train_node.py:498-573 (_correlation_calculation: every node's
+ * state dict saved to disk, loaded on rank 0, np.corrcoef per pair; disabled in the
+ * reference by a leading `return`), called from train_node.py:614-616.
+ */
+GA_API int ga_replica_gram(int dtype, const void* src, int64_t K, int64_t ld, int64_t n, double* gram,
+                           double* rowsum, double* dist2, void* work, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
