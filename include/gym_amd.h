@@ -280,6 +280,9 @@ GA_API int ga_sparta_torch_bernoulli(const int64_t* table, int32_t ntens, int64_
  * vals[j] = sum_k src_k[idx[j]], count[0] = number selected (int64),
  * count[1] = 1 if that exceeded `cap` (only the first cap are written).
  * `work` must hold ga_sparta_workspace_bytes(n) bytes.
+ * The sum is accumulated in fp32 in ascending replica order; with a bf16 set
+ * vals[j] holds that fp32 sum rounded once to bf16 (nearest even), and
+ * ga_sparta_scatter divides the rounded value.
  *
  * Replaces: RandomIndexSelector.get_indices (sparta.py:80-85), the mask
  * broadcast and gather of SparseCommunicator.communicate (sparta.py:24-38).
@@ -293,7 +296,10 @@ GA_API int ga_sparta_select(int dtype, const void* src, int64_t K, int64_t ld,
 
 /*
  * dst_k[idx[j]] = vals[j] / divisor for j < min(count[0], cap), k < K
- * (replica set in `layout`, GA_LAYOUT_*).
+ * (replica set in `layout`, GA_LAYOUT_*): a true fp32 division, rounded to the
+ * set's dtype.  With a bf16 set vals[j] is the bf16 that ga_sparta_select stored
+ * (the fp32 sum rounded once), so the select -> scatter path rounds twice where
+ * ga_sparta_average_local rounds once.
  * Replaces: `sparse_data /= num_nodes; param.masked_scatter_(mask, sparse_data)`
  * (sparta.py:40-42).
  */
@@ -307,7 +313,10 @@ GA_API int ga_sparta_scatter(int dtype, const void* vals, const int32_t* idx,
  * <- (sum over the K replicas) / divisor, in the same pass (the gathered lines
  * are written back while still in L2).  idx/vals/count/work may all be null
  * (no packed list, no count/scan pass); if given they are filled as by
- * ga_sparta_select.  Replaces sparta.py:24-44 for batched replicas.
+ * ga_sparta_select.  Any positive divisor (not only the replica count, not only
+ * powers of two) gives the correctly rounded quotient of the fp32 sum
+ * (ascending replica order), subnormal quotients included, rounded once to the
+ * set's dtype.  Replaces sparta.py:24-44 for batched replicas.
  */
 GA_API int ga_sparta_average_local(int dtype, void* reps, int64_t K, int64_t ld, int layout, int64_t n,
                                    const void* mask, int mask_format, uint64_t seed,

@@ -11,6 +11,7 @@ from oracle import diloco as odiloco
 from oracle import reduce as oreduce
 from oracle import sparta as osparta
 import demo_checks
+import sparta_checks
 
 pytestmark = pytest.mark.gpu
 
@@ -803,14 +804,11 @@ def test_sparta_bf16_and_many_replicas():
     for K, dtype in ((4, torch.bfloat16), (64, torch.float32)):
         x = np.random.default_rng(K).standard_normal((K, n)).astype(np.float32)
         src = t(x, dtype)
-        xs = src.float().cpu().numpy()
         m = osparta.philox_mask(n, 5, 6, p)
         ops.sparta_average_local(src, n, float(K), seed=5, iteration=6, p=p)
-        want = osparta.sparse_average(list(xs), m)
-        got = host(src)
-        tol = 1e-2 if dtype == torch.bfloat16 else 0
-        for k in range(K):
-            np.testing.assert_allclose(got[k], want[k], rtol=tol, atol=tol)
+        # bit for bit: the fp32 sums of the (dtype-rounded) inputs, divided, rounded once
+        want = sparta_checks.expect_fused(x, m, float(K), dtype)
+        assert np.array_equal(sparta_checks.bits_of(host(src)), sparta_checks.bits_of(want))
 
 
 @pytest.mark.parametrize("K,dtype,ld", [(8, torch.bfloat16, 8), (32, torch.bfloat16, 32), (12, torch.float32, 16),
@@ -824,7 +822,6 @@ def test_sparta_element_major_vector_rows(K, dtype, ld):
     x = np.random.default_rng(K + ld).standard_normal((K, n)).astype(np.float32)
     buf = torch.full((n, ld), 7.0, device=DEV, dtype=dtype)
     buf[:, :K] = t(np.ascontiguousarray(x.T), dtype)
-    xs = buf[:, :K].float().cpu().numpy().T
     m = osparta.philox_mask(n, 21, 4, p)
     cap = int(m.sum()) + 8
     idx, count, work = _sparta_buffers(n, cap)
@@ -833,18 +830,23 @@ def test_sparta_element_major_vector_rows(K, dtype, ld):
                              count=count, work=work, layout="elem")
     c = int(count[0].item())
     assert c == int(m.sum()) and np.array_equal(idx[:c].cpu().numpy(), np.flatnonzero(m))
-    want = osparta.sparse_average(list(xs), m)
+    # bit for bit: one rounding of fp32_sum / K in the fused form; vals = the fp32 sum rounded once
+    bits = sparta_checks.bits_of
+    want = sparta_checks.expect_fused(x, m, float(K), dtype)
+    want_vals, want2 = sparta_checks.expect_two_step(x, m, float(K), dtype)
     got = buf.float().cpu().numpy()
-    tol = 1e-2 if dtype == torch.bfloat16 else 0
-    np.testing.assert_allclose(got[:, :K].T, np.stack(want), rtol=tol, atol=tol)
+    assert np.array_equal(bits(got[:, :K].T), bits(want))
     assert (got[:, K:] == 7.0).all()
+    assert np.array_equal(bits(host(vals)[:c]), bits(want_vals))
     # the multi-rank form: select + gather into the packed list, scatter back
     buf2 = torch.full((n, ld), 7.0, device=DEV, dtype=dtype)
     buf2[:, :K] = t(np.ascontiguousarray(x.T), dtype)
     ops.sparta_select(buf2[:, :K], n, cap, idx, vals, count, work, seed=21, iteration=4, p=p, layout="elem")
     ops.sparta_scatter(vals, idx, count, cap, float(K), buf2[:, :K], layout="elem")
+    # select rounds the sum to the dtype, the scatter divides that value and rounds again
+    assert np.array_equal(bits(host(vals)[:c]), bits(want_vals))
     got2 = buf2.float().cpu().numpy()
-    np.testing.assert_allclose(got2[:, :K].T, np.stack(want), rtol=tol, atol=tol)
+    assert np.array_equal(bits(got2[:, :K].T), bits(want2))
     assert (got2[:, K:] == 7.0).all()
 
 
@@ -945,9 +947,8 @@ def test_sparta_average_local_own_groups(K, dtype, ld, p):
         bufs.append(host(buf))
     assert np.array_equal(bufs[0], bufs[1])
     xs = bufs[0]  # untouched elements keep their (dtype-rounded) inputs
-    want = osparta.sparse_average(list(t(np.ascontiguousarray(x.T), dtype).float().cpu().numpy().T), m)
-    tol = 1e-2 if dtype == torch.bfloat16 else 0
-    np.testing.assert_allclose(xs[:, :K].T, np.stack(want), rtol=tol, atol=tol)
+    want = sparta_checks.expect_fused(x, m, float(K), dtype)  # bit for bit: fp32_sum / K rounded once
+    assert np.array_equal(sparta_checks.bits_of(xs[:, :K].T), sparta_checks.bits_of(want))
     assert (xs[:, K:] == 3.0).all()
 
 
