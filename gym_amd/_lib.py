@@ -93,6 +93,8 @@ SIGNATURES = {
     "ga_replica_gram_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "ga_replica_gram_chain": (c_i32, []),
     "ga_replica_gram": (c_i32, [c_i32, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "ga_replica_gram_centered_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "ga_replica_gram_centered": (c_i32, [c_i32, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),
 }
 
 _lib = None

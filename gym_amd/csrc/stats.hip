@@ -19,6 +19,14 @@
 // kWaveCols multiply-adds (the MFMA is a k-ordered fmaf chain); the four waves'
 // results are added in wave order and written as the workgroup's fp32 partial
 // (K*K + 2K values), and gram_final_kernel sums the partials in a fixed order in fp64.
+//
+// ga_replica_gram_centered (CEN) is the same walk over d_k = x_k - m instead of x_k:
+// the lane completes the node mean of its four columns before any row of the tile
+// goes to LDS, and writes f - m.  The Gram matrix of the centred values keeps the
+// pairwise distances and 1 - correlation of nodes that are 1e-3 and less apart,
+// which G_ii + G_jj - 2 G_ij and G_ij - s_i s_j / n from the plain Gram matrix cancel
+// away.  sum d_k and m . d_k take the registers of rowsum and dist2; sum m^2 and
+// sum m are two more per-lane accumulators (partial: K*K + 2K + 2 values).
 #include "ga_common.h"
 
 namespace ga {
@@ -38,6 +46,7 @@ static_assert(kWaveCols <= 4096, "chain bound of ga_replica_gram_chain()");
 
 inline int64_t gram_grid(int64_t n) { return n <= 0 ? 0 : ceil_div(n, kWgCols); }
 inline int64_t gram_partial_len(int64_t K) { return K * K + 2 * K; }
+inline int64_t gram_centered_partial_len(int64_t K) { return K * K + 2 * K + 2; }
 
 // Columns [col, col + 4) of one row, still in the arena's format (bf16 is widened where
 // the values are used, so the loads stay in flight until then); columns >= n are never
@@ -75,7 +84,8 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 // KP = 32: v_mfma_f32_32x32x2_f32, KP = 16: v_mfma_f32_16x16x4_f32 (K <= KP).
-template <typename T, int KP, bool VEC>
+// CEN: the centred form; rs[] then holds sum d_k, d2[] holds m . d_k, want_dist is unused.
+template <typename T, int KP, bool VEC, bool CEN>
 __global__ __launch_bounds__(kGramBlock) void gram_partial_kernel(const T* __restrict__ src, int K, int64_t ld,
                                                                   int64_t n, int want_dist,
                                                                   float* __restrict__ work) {
@@ -96,6 +106,7 @@ __global__ __launch_bounds__(kGramBlock) void gram_partial_kernel(const T* __res
         rs[k] = 0.f;
         d2[k] = 0.f;
     }
+    float mm = 0.f, ms = 0.f;  // CEN: sum m^2, sum m
     ga_f16v acc32 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     ga_f4 acc16a = {0.f, 0.f, 0.f, 0.f}, acc16b = {0.f, 0.f, 0.f, 0.f};
 
@@ -117,14 +128,22 @@ __global__ __launch_bounds__(kGramBlock) void gram_partial_kernel(const T* __res
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     m[e] += f[e];
-                    rs[k] += f[e];
+                    if constexpr (!CEN) rs[k] += f[e];
                 }
-                *reinterpret_cast<float4*>(my + k * kStride + 4 * lane) = make_float4(f[0], f[1], f[2], f[3]);
+                if constexpr (!CEN)
+                    *reinterpret_cast<float4*>(my + k * kStride + 4 * lane) = make_float4(f[0], f[1], f[2], f[3]);
             }
         }
-        if (want_dist) {
+        if (CEN || want_dist) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) m[e] = m[e] / fK;
+            if constexpr (CEN) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    mm = fmaf(m[e], m[e], mm);
+                    ms += m[e];
+                }
+            }
 #pragma unroll
             for (int k = 0; k < KP; ++k) {
                 if (k < K) {
@@ -133,8 +152,18 @@ __global__ __launch_bounds__(kGramBlock) void gram_partial_kernel(const T* __res
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float q = f[e] - m[e];
-                        d2[k] = fmaf(q, q, d2[k]);
+                        if constexpr (CEN) {
+                            // the mean is complete: the image takes f - m (0 at columns >= n,
+                            // where every row reads as 0)
+                            f[e] = q;
+                            rs[k] += q;
+                            d2[k] = fmaf(m[e], q, d2[k]);
+                        } else {
+                            d2[k] = fmaf(q, q, d2[k]);
+                        }
                     }
+                    if constexpr (CEN)
+                        *reinterpret_cast<float4*>(my + k * kStride + 4 * lane) = make_float4(f[0], f[1], f[2], f[3]);
                 }
             }
         }
@@ -173,7 +202,7 @@ __global__ __launch_bounds__(kGramBlock) void gram_partial_kernel(const T* __res
         wave_lds_sync();
     }
 
-    // the wave's results into its own image: [KP x KP] Gram, rowsum, dist2
+    // the wave's results into its own image: [KP x KP] Gram, rowsum, dist2 (CEN: sum d, m . d, then sum m^2, sum m)
     float* out = my;
     if constexpr (KP == 32) {
 #pragma unroll
@@ -189,37 +218,49 @@ __global__ __launch_bounds__(kGramBlock) void gram_partial_kernel(const T* __res
     for (int k = 0; k < KP; ++k) {
         if (k < K) {
             const float s = wave_sum(rs[k]);
-            const float d = want_dist ? wave_sum(d2[k]) : 0.f;
+            const float d = (CEN || want_dist) ? wave_sum(d2[k]) : 0.f;
             if (lane == 0) {
                 out[KP * KP + k] = s;
                 out[KP * KP + KP + k] = d;
             }
         }
     }
+    constexpr int kExtra = CEN ? 2 : 0;
+    if constexpr (CEN) {
+        mm = wave_sum(mm);
+        ms = wave_sum(ms);
+        if (lane == 0) {
+            out[KP * KP + 2 * KP] = mm;
+            out[KP * KP + 2 * KP + 1] = ms;
+        }
+    }
     __syncthreads();
-    float* part = work + (int64_t)blockIdx.x * (K * K + 2 * K);
-    for (int i = threadIdx.x; i < KP * KP + 2 * KP; i += kGramBlock) {
+    float* part = work + (int64_t)blockIdx.x * (K * K + 2 * K + kExtra);
+    for (int i = threadIdx.x; i < KP * KP + 2 * KP + kExtra; i += kGramBlock) {
         float v = image[0][i];
 #pragma unroll
         for (int w = 1; w < kGramWaves; ++w) v += image[w][i];
         if (i < KP * KP) {
             const int row = i / KP, col = i % KP;
             if (row < K && col < K) part[row * K + col] = v;
-        } else {
+        } else if (i < KP * KP + 2 * KP) {
             const int which = (i - KP * KP) / KP, k = (i - KP * KP) % KP;
             if (k < K) part[K * K + which * K + k] = v;
+        } else {
+            part[K * K + 2 * K + (i - KP * KP - 2 * KP)] = v;
         }
     }
 }
 
 // out[e] = sum over the workgroups' partials of entry e, in fp64 and a fixed order:
 // slice s adds partials s, s + 32, ... ascending, the 32 slices are added ascending.
+// A partial holds P = K*K + 2K entries (gram, rowsum, dist2) and with `tail` two more.
 constexpr int kFinalEntries = 32, kFinalSlices = 32;
 __global__ __launch_bounds__(kFinalEntries * kFinalSlices) void gram_final_kernel(
     const float* __restrict__ work, int64_t nparts, int K, double* __restrict__ gram, double* __restrict__ rowsum,
-    double* __restrict__ dist2) {
+    double* __restrict__ dist2, double* __restrict__ tail) {
     __shared__ double red[kFinalSlices][kFinalEntries];
-    const int P = K * K + 2 * K;
+    const int P = K * K + 2 * K + (tail ? 2 : 0);
     const int ei = threadIdx.x % kFinalEntries, s = threadIdx.x / kFinalEntries;
     const int e = blockIdx.x * kFinalEntries + ei;
     double acc = 0.0;
@@ -234,24 +275,26 @@ __global__ __launch_bounds__(kFinalEntries * kFinalSlices) void gram_final_kerne
         for (int q = 1; q < kFinalSlices; ++q) v += red[q][ei];
         if (e < K * K) gram[e] = v;
         else if (e < K * K + K) rowsum[e - K * K] = v;
+        else if (e >= K * K + 2 * K) tail[e - K * K - 2 * K] = v;
         else if (dist2) dist2[e - K * K - K] = v;
     }
 }
 
 static bool gram_aligned(const void* p, int bytes) { return ((uintptr_t)p % bytes) == 0; }
 
-template <typename T>
+// CEN: gram = cgram, rowsum = dsum, dist2 = mdot, tail = mstat.
+template <typename T, bool CEN>
 static int launch_gram(const void* src, int64_t K, int64_t ld, int64_t n, double* gram, double* rowsum,
-                       double* dist2, void* work, hipStream_t stream) {
+                       double* dist2, double* tail, void* work, hipStream_t stream) {
     const int vb = 4 * (int)sizeof(T);
     const bool vec = gram_aligned(src, vb) && (ld % 4 == 0 || K == 1);
     const int64_t grid = gram_grid(n);
     const int want = dist2 ? 1 : 0;
     const T* s = (const T*)src;
     float* w = (float*)work;
-#define GA_GRAM_LAUNCH(KP, VEC)                                                                              \
-    hipLaunchKernelGGL((gram_partial_kernel<T, KP, VEC>), dim3((unsigned)grid), dim3(kGramBlock), 0, stream, \
-                       s, (int)K, ld, n, want, w)
+#define GA_GRAM_LAUNCH(KP, VEC)                                                                            \
+    hipLaunchKernelGGL((gram_partial_kernel<T, KP, VEC, CEN>), dim3((unsigned)grid), dim3(kGramBlock), 0, \
+                       stream, s, (int)K, ld, n, want, w)
     if (K > 16) {
         if (vec) GA_GRAM_LAUNCH(32, true);
         else GA_GRAM_LAUNCH(32, false);
@@ -260,13 +303,13 @@ static int launch_gram(const void* src, int64_t K, int64_t ld, int64_t n, double
         else GA_GRAM_LAUNCH(16, false);
     }
 #undef GA_GRAM_LAUNCH
-    int rc = check_launch("ga_replica_gram");
+    int rc = check_launch(CEN ? "ga_replica_gram_centered" : "ga_replica_gram");
     if (rc != GA_OK) return rc;
-    const int P = (int)gram_partial_len(K);
+    const int P = (int)(CEN ? gram_centered_partial_len(K) : gram_partial_len(K));
     hipLaunchKernelGGL(gram_final_kernel, dim3((unsigned)ceil_div(P, kFinalEntries)),
                        dim3(kFinalEntries * kFinalSlices), 0, stream, (const float*)w, grid, (int)K, gram, rowsum,
-                       dist2);
-    return check_launch("ga_replica_gram (final sum)");
+                       dist2, tail);
+    return check_launch(CEN ? "ga_replica_gram_centered (final sum)" : "ga_replica_gram (final sum)");
 }
 
 }  // namespace ga
@@ -306,6 +349,44 @@ extern "C" GA_API int ga_replica_gram(int dtype, const void* src, int64_t K, int
     GA_REQUIRE(K == 1 || ld >= n, "ga_replica_gram: ld %lld < n %lld", (long long)ld, (long long)n);
     GA_REQUIRE(gram_aligned(src, dtype == GA_F32 ? 4 : 2), "ga_replica_gram: src is not element aligned");
     GA_REQUIRE(gram_grid(n) < (int64_t)INT32_MAX, "ga_replica_gram: n too large");
-    if (dtype == GA_F32) return launch_gram<float>(src, K, ld, n, gram, rowsum, dist2, work, stream);
-    return launch_gram<__hip_bfloat16>(src, K, ld, n, gram, rowsum, dist2, work, stream);
+    if (dtype == GA_F32) return launch_gram<float, false>(src, K, ld, n, gram, rowsum, dist2, nullptr, work, stream);
+    return launch_gram<__hip_bfloat16, false>(src, K, ld, n, gram, rowsum, dist2, nullptr, work, stream);
+}
+
+extern "C" GA_API int64_t ga_replica_gram_centered_workspace_bytes(int64_t K, int64_t n) {
+    if (K < 1 || K > kGramMaxK || n < 0) return -1;
+    return gram_grid(n) * gram_centered_partial_len(K) * (int64_t)sizeof(float);
+}
+
+extern "C" GA_API int ga_replica_gram_centered(int dtype, const void* src, int64_t K, int64_t ld, int64_t n,
+                                               double* cgram, double* mdot, double* dsum, double* mstat,
+                                               void* work, hipStream_t stream) {
+    clear_error();
+    GA_REQUIRE(n >= 0 && K >= 1, "ga_replica_gram_centered: bad sizes n=%lld K=%lld", (long long)n, (long long)K);
+    if (K > kGramMaxK) {
+        set_error("ga_replica_gram_centered: K=%lld replicas, at most %d are supported", (long long)K, kGramMaxK);
+        return GA_EUNSUP;
+    }
+    GA_REQUIRE(dtype == GA_F32 || dtype == GA_BF16, "ga_replica_gram_centered: unknown dtype %d", dtype);
+    GA_REQUIRE(gram_aligned(cgram, 8) && gram_aligned(mdot, 8) && gram_aligned(dsum, 8) && gram_aligned(mstat, 8) &&
+                   gram_aligned(work, 4),
+               "ga_replica_gram_centered: outputs must be 8-byte aligned, the workspace 4-byte aligned");
+    if (n == 0) {
+        hipError_t e = hipSuccess;
+        if (cgram) e = hipMemsetAsync(cgram, 0, (size_t)(K * K) * sizeof(double), stream);
+        if (e == hipSuccess && mdot) e = hipMemsetAsync(mdot, 0, (size_t)K * sizeof(double), stream);
+        if (e == hipSuccess && dsum) e = hipMemsetAsync(dsum, 0, (size_t)K * sizeof(double), stream);
+        if (e == hipSuccess && mstat) e = hipMemsetAsync(mstat, 0, 2 * sizeof(double), stream);
+        if (e != hipSuccess) {
+            set_error("ga_replica_gram_centered: hipMemsetAsync failed: %s", hipGetErrorString(e));
+            return GA_EHIP;
+        }
+        return GA_OK;
+    }
+    GA_REQUIRE(src && cgram && mdot && dsum && mstat && work, "ga_replica_gram_centered: null buffer");
+    GA_REQUIRE(K == 1 || ld >= n, "ga_replica_gram_centered: ld %lld < n %lld", (long long)ld, (long long)n);
+    GA_REQUIRE(gram_aligned(src, dtype == GA_F32 ? 4 : 2), "ga_replica_gram_centered: src is not element aligned");
+    GA_REQUIRE(gram_grid(n) < (int64_t)INT32_MAX, "ga_replica_gram_centered: n too large");
+    if (dtype == GA_F32) return launch_gram<float, true>(src, K, ld, n, cgram, dsum, mdot, mstat, work, stream);
+    return launch_gram<__hip_bfloat16, true>(src, K, ld, n, cgram, dsum, mdot, mstat, work, stream);
 }

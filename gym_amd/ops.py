@@ -109,6 +109,35 @@ def replica_gram(src, n=None, want_dist=True):
     return gram, rowsum, dist2
 
 
+def replica_gram_centered(src, n=None):
+    """(cgram [K, K], mdot [K], dsum [K], mstat [2]) of the first n elements of the
+    rows of a replica set [K, ld] (or one 1-D replica), float64 on src's device.
+    With m = the node mean and d_k = x_k - m in fp32: cgram[i, j] = d_i . d_j,
+    mdot[k] = m . d_k, dsum[k] = sum d_k, mstat = (m . m, sum m)
+    (ga_replica_gram_centered, one read of src; K <= 32)."""
+    src2 = _as2d(src)
+    _gpu(src2)
+    K, ld = _rows_ld(src2)
+    if src2.stride(1) != 1:
+        raise ValueError("replica_gram_centered: rows must be contiguous")
+    n = src2.shape[1] if n is None else int(n)
+    if n < 0 or n > src2.shape[1]:
+        raise ValueError("replica_gram_centered: n exceeds the row length")
+    code = _dtype_code(src2)
+    nbytes = int(lib().ga_replica_gram_centered_workspace_bytes(K, n))
+    if nbytes < 0:
+        raise ValueError(f"replica_gram_centered: {K} replicas, at most {GRAM_MAX_K} are supported")
+    dev = src2.device
+    cgram = torch.empty(K, K, dtype=torch.float64, device=dev)
+    mdot = torch.empty(K, dtype=torch.float64, device=dev)
+    dsum = torch.empty(K, dtype=torch.float64, device=dev)
+    mstat = torch.empty(2, dtype=torch.float64, device=dev)
+    work = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=dev)
+    check(lib().ga_replica_gram_centered(code, _p(src2), K, ld, n, _p(cgram), _p(mdot), _p(dsum), _p(mstat),
+                                         _p(work), _stream()), "ga_replica_gram_centered")
+    return cgram, mdot, dsum, mstat
+
+
 def diloco_outer(src, master, mom, dst, n, divisor, lr, momentum, dampening, weight_decay, nesterov,
                  first_step):
     """Fused DiLoCo outer step over [0, n) of master/mom (see include/gym_amd.h)."""

@@ -545,7 +545,7 @@ class ReplicaTrainNode:
     def __init__(self, model, train_dataset, val_dataset, strategy, device, rank, num_nodes, K, num_epochs,
                  max_steps=None, batch_size=16, minibatch_size=16, val_size=64, val_interval=100, shuffle=True,
                  autocast=False, replica_forward="loop", replica_vmap_chunk=None, correlation_interval=None,
-                 **kwargs):
+                 drift_detail=False, **kwargs):
         from .train_node import RunLog
         seed = kwargs.get("seed", 42)
         torch.manual_seed(seed)
@@ -584,6 +584,7 @@ class ReplicaTrainNode:
         self.local_step = 0
         self.logger = RunLog(strategy, max_steps) if rank == 0 else None
         self.correlation_interval = correlation_interval
+        self.drift_detail = drift_detail
         self.drift = None  # NodeDrift, built at the first measurement (correlation_interval set)
 
     def _next(self, k):
@@ -666,15 +667,21 @@ class ReplicaTrainNode:
     def _node_drift(self):
         """Model correlation and consensus distance over all num_nodes nodes
         (train_node.py:498-573 through ga_replica_gram on the replica arena):
-        every process calls it, the first records the two numbers."""
+        every process calls it, the first records the two numbers, and with
+        drift_detail (ga_replica_gram_centered) avg_model_decorrelation and
+        max_pairwise_distance as well."""
         from .metrics import NodeDrift
         ra = self.runner.ra
         if self.drift is None:
-            self.drift = NodeDrift(self.runner.coll, self.K, ra.ld, ra.ld, ra.layout.n_params, ra.device, ra.dtype)
+            self.drift = NodeDrift(self.runner.coll, self.K, ra.ld, ra.ld, ra.layout.n_params, ra.device, ra.dtype,
+                                   detail=self.drift_detail)
         out = self.drift(ra.flat_set)
         if out is not None and self.logger is not None:
             self.logger.log_metric("avg_model_correlation", out["avg_model_correlation"])
             self.logger.log_metric("consensus_distance", out["consensus_distance"])
+            if self.drift_detail:
+                self.logger.log_metric("avg_model_decorrelation", out["avg_model_decorrelation"])
+                self.logger.log_metric("max_pairwise_distance", out["max_pairwise_distance"])
         return out
 
     def train(self):

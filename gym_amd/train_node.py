@@ -69,7 +69,7 @@ class TrainNode(LogModule):
                  strategy: Strategy, device: torch.device, rank: int, num_nodes: int, num_epochs: int,
                  max_steps: int = None, batch_size: int = 16, minibatch_size: int = 16, val_size: int = 64,
                  val_interval: int = 100, checkpoint_interval: int = 100, autocast: bool = False,
-                 correlation_interval: int = None, **kwargs):
+                 correlation_interval: int = None, drift_detail: bool = False, **kwargs):
         seed = kwargs.get("seed", 42)
         torch.manual_seed(seed)
         torch.cuda.manual_seed(seed)
@@ -95,6 +95,7 @@ class TrainNode(LogModule):
         self.autocast = autocast
         self.checkpoint_interval = checkpoint_interval
         self.correlation_interval = correlation_interval
+        self.drift_detail = drift_detail
         self.kwargs = kwargs
         self.build_dataloaders()
         torch.manual_seed(42)
@@ -206,7 +207,9 @@ class TrainNode(LogModule):
     def _node_drift(self):
         """Model correlation and consensus distance over the nodes
         (train_node.py:498-573 through ga_replica_gram): every rank calls it,
-        rank 0 records the two numbers.  The vector is the strategy's parameter
+        rank 0 records the two numbers, and with drift_detail (through
+        ga_replica_gram_centered) avg_model_decorrelation and
+        max_pairwise_distance as well.  The vector is the strategy's parameter
         arena, or a flat copy of model.parameters() for a strategy without one."""
         from .comm import Collective
         from .metrics import NodeDrift, flat_parameters
@@ -216,11 +219,15 @@ class TrainNode(LogModule):
         else:
             flat, n_true = flat_parameters(self.model)
         if self.drift is None:
-            self.drift = NodeDrift(Collective(), 1, flat.numel(), flat.numel(), n_true, flat.device, flat.dtype)
+            self.drift = NodeDrift(Collective(), 1, flat.numel(), flat.numel(), n_true, flat.device, flat.dtype,
+                                   detail=self.drift_detail)
         out = self.drift(flat)
         if out is not None and self.rank == 0 and self.logger is not None:
             self.logger.log_metric("avg_model_correlation", out["avg_model_correlation"])
             self.logger.log_metric("consensus_distance", out["consensus_distance"])
+            if self.drift_detail:
+                self.logger.log_metric("avg_model_decorrelation", out["avg_model_decorrelation"])
+                self.logger.log_metric("max_pairwise_distance", out["max_pairwise_distance"])
         return out
 
     def train(self):

@@ -522,6 +522,41 @@ GA_API int ga_replica_gram_chain(void);
 GA_API int ga_replica_gram(int dtype, const void* src, int64_t K, int64_t ld, int64_t n, double* gram,
                            double* rowsum, double* dist2, void* work, hipStream_t stream);
 
+/* Bytes of the `work` buffer ga_replica_gram_centered needs (one fp32 partial of
+ * K*K + 2K + 2 values per workgroup of 16384 columns); -1 for K outside 1..32 or n < 0. */
+GA_API int64_t ga_replica_gram_centered_workspace_bytes(int64_t K, int64_t n);
+
+/*
+ * ga_replica_gram's one read of src [K, ld] (K <= 32, n elements per row, f32 or
+ * bf16 widened to f32), taken over the centred values.  With
+ *   m[e]   = (fp32 sum of x_k[e] in ascending k) / K   (true division, dist2's rule)
+ *   d_k[e] = x_k[e] - m[e]                              (fp32)
+ * it gives, in fp64 on the device:
+ *   cgram[i*K + j] = sum_e d_i[e] * d_j[e]   (the full symmetric K x K matrix, f32 MFMA)
+ *   mdot[k]        = sum_e m[e] * d_k[e]
+ *   dsum[k]        = sum_e d_k[e]
+ *   mstat[0]       = sum_e m[e]^2,  mstat[1] = sum_e m[e]
+ * so x_i . x_j = mstat[0] + mdot[i] + mdot[j] + cgram[i*K + j] and sum x_k =
+ * mstat[1] + dsum[k], but the large common part m is kept apart from the small
+ * differences d: cgram_ii + cgram_jj - 2 cgram_ij is |x_i - x_j|^2 and the host's
+ * 1 - corr_ij (gym_amd/metrics.py) stay accurate when the nodes are 1e-3 and less
+ * apart, where gram_ii + gram_jj - 2 gram_ij and gram_ij - rowsum_i rowsum_j / n
+ * cancel.  cgram[k*K + k] is ga_replica_gram's dist2[k].  The node mean of a column
+ * is complete before any row of its tile is used; everything else is
+ * ga_replica_gram's: MFMA shapes, fp32 partials in `work`
+ * (ga_replica_gram_centered_workspace_bytes), the fixed-order fp64 final sum, no
+ * atomics and the same bits for the same input, ga_replica_gram_chain() as the chain
+ * bound L of every fp32 accumulator, elements at index >= n never read, 16-byte
+ * (bf16: 8-byte) vector loads when src is so aligned and ld % 4 == 0 and element
+ * loads otherwise with the same results.  n == 0 zeroes the (non-null) outputs;
+ * otherwise all four are required.  K > 32: GA_EUNSUP.
+ *
+ * Replaces: exogym/train_node.py:498-573 (_correlation_calculation's np.corrcoef
+ * per pair, which works in float64 and so resolves close nodes).
+ */
+GA_API int ga_replica_gram_centered(int dtype, const void* src, int64_t K, int64_t ld, int64_t n, double* cgram,
+                                    double* mdot, double* dsum, double* mstat, void* work, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

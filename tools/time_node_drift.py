@@ -3,6 +3,8 @@ K = 8 and K = 32 replicas beside ga_stream_copy of the same bytes in the same
 process: queued back-to-back launches between two device events.  Prints one JSON
 line per K: milliseconds per launch, the bytes the kernel reads over that time as
 a fraction of 8 TB/s, and the copy's figures (a copy moves the bytes twice).
+A second line per K times ga_replica_gram_centered (drift_detail=True) on the same
+rows, alternated with ga_replica_gram with dist2, and gives the ratio of the two.
 
     python tools/time_node_drift.py [--reps 20] [--ks 8,32] [--dtype fp32|bf16]
 """
@@ -66,6 +68,17 @@ def main():
                                          d2.data_ptr() if d2 is not None else None, work.data_ptr(), stream),
                        "ga_replica_gram")
 
+        cgram = torch.empty(K, K, dtype=torch.float64, device=dev)
+        mdot = torch.empty(K, dtype=torch.float64, device=dev)
+        dsum = torch.empty(K, dtype=torch.float64, device=dev)
+        mstat = torch.empty(2, dtype=torch.float64, device=dev)
+        cwork = torch.empty(L.ga_replica_gram_centered_workspace_bytes(K, ld) // 4, dtype=torch.float32, device=dev)
+
+        def run_centered():
+            _lib.check(L.ga_replica_gram_centered(code, src.data_ptr(), K, ld, ld, cgram.data_ptr(), mdot.data_ptr(),
+                                                  dsum.data_ptr(), mstat.data_ptr(), cwork.data_ptr(), stream),
+                       "ga_replica_gram_centered")
+
         ms = timed(lambda: run(dist2), a.reps)
         ms_nodist = timed(lambda: run(None), a.reps)
         dst = torch.empty_like(src)
@@ -79,7 +92,18 @@ def main():
             "stream_copy_frac_of_8TBps": round(2 * nbytes / (ms_copy * 1e-3) / PEAK, 4),
             "gram_ms_over_copy_ms": round(ms / ms_copy, 3),
         }), flush=True)
-        del src, work
+        # the two kernels alternated on the same rows: the spread of the rounds is the noise
+        rounds = [(timed(lambda: run(dist2), a.reps), timed(run_centered, a.reps)) for _ in range(3)]
+        ms_plain = sum(r[0] for r in rounds) / len(rounds)
+        ms_cen = sum(r[1] for r in rounds) / len(rounds)
+        print(json.dumps({
+            "kernel": "ga_replica_gram_centered", "model": a.model, "dtype": a.dtype, "K": K, "ld": ld,
+            "bytes_read": nbytes, "ms": round(ms_cen, 4), "frac_of_8TBps": round(nbytes / (ms_cen * 1e-3) / PEAK, 4),
+            "gram_with_dist2_ms": round(ms_plain, 4), "centered_ms_over_gram_ms": round(ms_cen / ms_plain, 3),
+            "rounds_ms_gram_centered": [[round(p, 4), round(c, 4)] for p, c in rounds],
+            "stream_copy_ms": round(ms_copy, 4), "centered_ms_over_copy_ms": round(ms_cen / ms_copy, 3),
+        }), flush=True)
+        del src, work, cwork
 
 
 if __name__ == "__main__":
