@@ -6,8 +6,8 @@ implementation, so `from exogym import LocalTrainer` and
 `from exogym.strategy import DiLoCoStrategy` work unchanged.  Every submodule
 (exogym.trainer, exogym.strategy.sparta, ...) IS the gym_amd module of the same
 name.  Not provided: exogym.logger (wandb/CSV logging, out of scope; gym_amd
-records a run in memory) and SPARTADiLoCoStrategy (not importable in the
-reference either: sparta_diloco.py:6).
+records a run in memory).  SPARTADiLoCoStrategy, which the reference cannot
+import (sparta_diloco.py:6), is provided (exogym.strategy.sparta_diloco).
 """
 from gym_amd.train_node import TrainNode
 from gym_amd.trainer import LocalTrainer, Trainer

@@ -2,10 +2,12 @@
 
 The reference's __all__ also lists "SPARTADiLoCoStrategy", whose import is
 commented out (exogym/strategy/__init__.py:10,20), so `from exogym.strategy
-import *` raises AttributeError there; here __all__ holds the names that exist.
+import *` raises AttributeError there; here the name resolves, and
+DiLoCoCommunicator (the name its module fails to import) is exported beside it.
 """
-from gym_amd.strategy import (CommunicateOptimizeStrategy, DeMoStrategy, DiLoCoStrategy, FedAvgStrategy, OptimSpec,
-                              SimpleReduceStrategy, SPARTAStrategy, Strategy)
+from gym_amd.strategy import (CommunicateOptimizeStrategy, DeMoStrategy, DiLoCoCommunicator, DiLoCoStrategy,
+                              FedAvgStrategy, OptimSpec, SimpleReduceStrategy, SPARTADiLoCoStrategy, SPARTAStrategy,
+                              Strategy)
 
 __all__ = [
     "Strategy",
@@ -15,4 +17,6 @@ __all__ = [
     "FedAvgStrategy",
     "CommunicateOptimizeStrategy",
     "DeMoStrategy",
+    "SPARTADiLoCoStrategy",
+    "DiLoCoCommunicator",
 ]

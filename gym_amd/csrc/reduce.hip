@@ -144,6 +144,85 @@ __global__ __launch_bounds__(kBlock) void diloco_outer_kernel(
     }
 }
 
+// The value an arena of dtype T holds after storing x (SPARTA writes its average
+// to the replicas before the outer step reads them back).
+template <typename T> __device__ __forceinline__ float round_to(float x);
+template <> __device__ __forceinline__ float round_to<float>(float x) { return x; }
+template <> __device__ __forceinline__ float round_to<__hip_bfloat16>(float x) {
+    return __bfloat162float(__float2bfloat16(x));
+}
+
+// What the outer step sums over an element SPARTA averaged just before it: every
+// replica then holds a = sum / sparse_divisor rounded to T, and the ascending
+// fp32 sum of K copies of a is K additions (not K * a: the partial sums round).
+template <typename T>
+__device__ __forceinline__ float sum_of_sparse_average(float sum, float sparse_divisor, int64_t K) {
+    const float a = round_to<T>(sum / sparse_divisor);
+    float s = 0.f;
+    for (int64_t k = 0; k < K; ++k) s += a;
+    return s;
+}
+
+// SPARTA's sparse average followed by the outer step, in the outer step's one pass
+// (ga_diloco_outer_masked): diloco_outer_kernel in place over all K rows, with the
+// elements whose bit is set in `bits` (bit j of word w = element 64 w + j) taking
+// sum_of_sparse_average.  A lane's 4 elements are one nibble of a word, the 16
+// lanes of a word load the same 8 bytes; at SPARTA's rates the nibble is almost
+// always 0 and the selected branch is skipped.
+template <typename T, typename M, bool VEC>
+__global__ __launch_bounds__(kBlock) void diloco_outer_masked_kernel(
+    T* src, int64_t K, int64_t ld, int64_t n, const uint64_t* __restrict__ bits, float sparse_divisor,
+    M* master, M* mom, OuterParams op) {
+    const bool has_mom = op.momentum != 0.f;
+    int64_t lo, hi;
+    if constexpr (VEC) {
+        using V = typename Vec4<T>::type;
+        using VM = typename Vec4<M>::type;
+        chunk_range(n >> 2, lo, hi);
+        for (int64_t v = lo + threadIdx.x; v < hi; v += kBlock) {
+            const uint32_t nib = (uint32_t)(bits[v >> 4] >> ((v & 15) * 4)) & 0xfu;
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8
+            for (int64_t k = 0; k < K; ++k) {
+                float f[4];
+                Vec4<T>::unpack(stream_load(reinterpret_cast<const V*>(src + k * ld) + v), f);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e] += f[e];
+            }
+            if (nib) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (nib >> e & 1u) acc[e] = sum_of_sparse_average<T>(acc[e], sparse_divisor, K);
+            }
+            float m[4], b[4] = {0.f, 0.f, 0.f, 0.f};
+            Vec4<M>::unpack(stream_load(reinterpret_cast<const VM*>(master) + v), m);
+            if (has_mom && !op.first_step) Vec4<M>::unpack(stream_load(reinterpret_cast<const VM*>(mom) + v), b);
+            float out[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) out[e] = outer_update(acc[e], m[e], b[e], op);
+            const V o = Vec4<T>::pack(out);
+            const uint32_t i = (uint32_t)(v - lo);
+            store_sc1(reinterpret_cast<VM*>(master) + lo, i, Vec4<M>::pack(m));
+            if (has_mom) store_sc1(reinterpret_cast<VM*>(mom) + lo, i, Vec4<M>::pack(b));
+            for (int64_t j = 0; j < K; ++j) store_sc1(reinterpret_cast<V*>(src + j * ld) + lo, i, o);
+        }
+    } else {
+        chunk_range(n, lo, hi);
+        for (int64_t i = lo + threadIdx.x; i < hi; i += kBlock) {
+            float acc = 0.f;
+#pragma unroll 4
+            for (int64_t k = 0; k < K; ++k) acc += Elem<T>::load(src + k * ld + i);
+            if (bits[i >> 6] >> (i & 63) & 1ull) acc = sum_of_sparse_average<T>(acc, sparse_divisor, K);
+            float m = Elem<M>::load(master + i);
+            float b = (has_mom && !op.first_step) ? Elem<M>::load(mom + i) : 0.f;
+            const float out = outer_update(acc, m, b, op);
+            Elem<M>::store(master + i, m);
+            if (has_mom) Elem<M>::store(mom + i, b);
+            for (int64_t j = 0; j < K; ++j) Elem<T>::store(src + j * ld + i, out);
+        }
+    }
+}
+
 // Placement probe of the fused outer step (no reference counterpart): the exact
 // access pattern of diloco_outer_kernel<float, float, true> -- workgroup b's block
 // of K replica streams, master and momentum read, the same blocks written through
@@ -231,6 +310,22 @@ static int launch_diloco(const void* src, int64_t K, int64_t ld_src, int64_t n, 
     return check_launch("ga_diloco_outer");
 }
 
+template <typename T, typename M>
+static int launch_diloco_masked(void* src, int64_t K, int64_t ld, int64_t n, const uint64_t* bits,
+                                float sparse_divisor, void* master, void* mom, const OuterParams& op,
+                                hipStream_t stream) {
+    const bool vec = (n % 4 == 0) && (ld % 4 == 0) && aligned(src, 4 * (int)sizeof(T)) &&
+                     aligned(master, 4 * (int)sizeof(M)) && aligned(mom, 4 * (int)sizeof(M));
+    if (vec) {
+        hipLaunchKernelGGL((diloco_outer_masked_kernel<T, M, true>), dim3(chunk_grid(n / 4)), dim3(kBlock), 0,
+                           stream, (T*)src, K, ld, n, bits, sparse_divisor, (M*)master, (M*)mom, op);
+    } else {
+        hipLaunchKernelGGL((diloco_outer_masked_kernel<T, M, false>), dim3(chunk_grid(n)), dim3(kBlock), 0,
+                           stream, (T*)src, K, ld, n, bits, sparse_divisor, (M*)master, (M*)mom, op);
+    }
+    return check_launch("ga_diloco_outer_masked");
+}
+
 }  // namespace ga
 
 using namespace ga;
@@ -292,6 +387,43 @@ extern "C" GA_API int ga_diloco_outer(int dtype, const void* src, int64_t K, int
                                                                  dst, K_out, ld_dst, stream);
         default:
             set_error("ga_diloco_outer: unknown dtype %d", dtype);
+            return GA_EINVAL;
+    }
+}
+
+extern "C" GA_API int ga_diloco_outer_masked(int dtype, void* src, int64_t K, int64_t ld_src, int64_t n,
+                                             const uint64_t* bits, float sparse_divisor, float divisor,
+                                             void* master, void* mom, int master_f32, int first_step,
+                                             float lr, float momentum, float dampening, float weight_decay,
+                                             int nesterov, void* dst, int64_t K_out, int64_t ld_dst,
+                                             hipStream_t stream) {
+    clear_error();
+    GA_REQUIRE(n >= 0 && K >= 1, "ga_diloco_outer_masked: bad sizes n=%lld K=%lld", (long long)n, (long long)K);
+    // the sparse average only vanishes into the outer step when that overwrites every row it wrote
+    GA_REQUIRE(dst == src && K_out == K && (K == 1 || ld_dst == ld_src),
+               "ga_diloco_outer_masked: the step must run in place over all K rows (dst == src, K_out == K = %lld, "
+               "ld_dst == ld_src); got K_out=%lld", (long long)K, (long long)K_out);
+    GA_REQUIRE(sparse_divisor > 0.0f, "ga_diloco_outer_masked: sparse_divisor must be > 0");
+    GA_REQUIRE(divisor != 0.0f, "ga_diloco_outer_masked: divisor is 0");
+    if (n == 0) return GA_OK;
+    GA_REQUIRE(bits != nullptr, "ga_diloco_outer_masked: null mask words");
+    GA_REQUIRE(src && master, "ga_diloco_outer_masked: null src/master");
+    GA_REQUIRE(momentum == 0.0f || mom, "ga_diloco_outer_masked: momentum != 0 needs a momentum buffer");
+    GA_REQUIRE(K == 1 || ld_src >= n, "ga_diloco_outer_masked: ld_src < n");
+    GA_REQUIRE(!(nesterov && (momentum <= 0.0f || dampening != 0.0f)),
+               "ga_diloco_outer_masked: Nesterov momentum requires a momentum and zero dampening");
+    GA_REQUIRE(dtype == GA_F32 || master_f32, "ga_diloco_outer_masked: master and momentum must be fp32");
+    OuterParams op{divisor, lr, momentum, dampening, weight_decay, first_step ? 1 : 0, nesterov ? 1 : 0};
+    if (momentum == 0.0f) mom = nullptr;
+    switch (dtype) {
+        case GA_F32:
+            return launch_diloco_masked<float, float>(src, K, ld_src, n, bits, sparse_divisor, master, mom, op,
+                                                      stream);
+        case GA_BF16:
+            return launch_diloco_masked<__hip_bfloat16, float>(src, K, ld_src, n, bits, sparse_divisor, master,
+                                                               mom, op, stream);
+        default:
+            set_error("ga_diloco_outer_masked: unknown dtype %d", dtype);
             return GA_EINVAL;
     }
 }

@@ -385,10 +385,24 @@ class DiLoCoOuter:
                       "how": "the caller's replica set moved to the fastest of fresh [K, ld] allocations "
                              "(probed against the ordinary master); candidate 0 = where it was"}
 
-    def __call__(self, reps):
+    def __call__(self, reps, sparse_mask=None):
+        """sparse_mask: packed int64 mask words (ops.sparta_pack_mask layout) of a
+        SPARTA sparse average over all K_total nodes that this step also performs,
+        just before the outer update, in the same pass (ga_diloco_outer_masked;
+        bit-identical to Sparta followed by this step).  Single process only."""
         n = self.n
         self.launch_elems = []
-        if not self.coll.exchange:  # one kernel: read every replica, update, write every replica
+        if sparse_mask is not None:
+            if self.coll.exchange:
+                raise ValueError("DiLoCoOuter: the masked outer step needs a local (no-exchange) step; run Sparta "
+                                 "and the outer step one after the other")
+            reps = self._place(reps)
+            h = self.hp
+            ops.diloco_outer_masked(reps[:, :n], sparse_mask, self.master, self.mom, n, float(self.K_total),
+                                    self.K_total, h["lr"], h["momentum"], h["dampening"], h["weight_decay"],
+                                    h["nesterov"], self.first)
+            self.launch_elems.append(n)
+        elif not self.coll.exchange:  # one kernel: read every replica, update, write every replica
             reps = self._place(reps)
             self._outer(reps[:, :n], self.K_total, reps[:, :n])
         elif not self.shard:  # gloo: all-reduce the sum, replicated update

@@ -161,6 +161,28 @@ def diloco_outer(src, master, mom, dst, n, divisor, lr, momentum, dampening, wei
           "ga_diloco_outer")
 
 
+def diloco_outer_masked(reps, bits, master, mom, n, sparse_divisor, divisor, lr, momentum, dampening, weight_decay,
+                        nesterov, first_step):
+    """SPARTA's sparse average over the elements selected in `bits` (packed int64
+    words, sparta_pack_mask layout) followed by the fused DiLoCo outer step, in
+    place over every row of reps, as one pass (ga_diloco_outer_masked):
+    bit-identical to sparta_average_local(reps, n, sparse_divisor, mask=bits)
+    then diloco_outer(reps, ..., dst=reps)."""
+    r2 = _as2d(reps)
+    _gpu(r2, bits, master, mom)
+    K, ld = _rows_ld(r2)
+    if master.numel() < n or (mom is not None and mom.numel() < n) or r2.shape[1] < n:
+        raise ValueError("diloco_outer_masked: buffers shorter than n")
+    if bits.dtype != torch.int64 or bits.numel() < sparta_mask_words(n) or not bits.is_contiguous():
+        raise ValueError("diloco_outer_masked: bits must be a contiguous int64 tensor of >= ceil(n/64) words")
+    if master.dtype != torch.float32 or (mom is not None and mom.dtype != torch.float32):
+        raise TypeError("diloco_outer_masked: master and momentum must be float32")
+    check(lib().ga_diloco_outer_masked(_dtype_code(r2), _p(r2), K, ld, int(n), _p(bits), float(sparse_divisor),
+                                       float(divisor), _p(master), _p(mom), 1, int(bool(first_step)), float(lr),
+                                       float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)),
+                                       _p(r2), K, ld, _stream()), "ga_diloco_outer_masked")
+
+
 def sparta_gap_table(p):
     """The 64-entry gap table of the Philox mask stream (include/gym_amd.h)."""
     import ctypes

@@ -16,8 +16,10 @@ minibatch_size`, its own clip_grad_norm_, then the strategy step.  Supported
 strategies: SimpleReduce, DiLoCo (any outer optimizer: the fused kernel for
 SGD-family, torch's optimizer on an fp32 master otherwise), SPARTA (every
 selector: the torch-drawn masks of node 0 -- the reference uses rank 0's --
-or the Philox stream), FedAvg (full or island averaging), DeMo.  Anything else runs on
-the process-per-node path (ReplicaRunner.supports).
+or the Philox stream), FedAvg (full or island averaging), DeMo, SPARTA+DiLoCo (SPARTA's
+average and DiLoCo's outer step as above; in one process a step where both fire is
+one pass, ga_diloco_outer_masked).  Anything else runs on the process-per-node path
+(ReplicaRunner.supports).
 
 The K nodes' forward/backward passes run one node after the other by default
 (replica_forward="loop": each node's gradients bit-identical to its own
@@ -45,6 +47,7 @@ from .strategy.demo import DeMoStrategy
 from .strategy.diloco import DiLoCoStrategy, fused_sgd_hparams
 from .strategy.federated_averaging import FedAvgStrategy
 from .strategy.sparta import MaskDraw, RandomIndexSelector, SPARTAStrategy, draw_masks
+from .strategy.sparta_diloco import SPARTADiLoCoStrategy
 from .strategy.strategy import SimpleReduceStrategy, clip_arena_grad_norm_
 
 
@@ -92,7 +95,7 @@ class ReplicaRunner:
 
     @staticmethod
     def supports(strategy):
-        if isinstance(strategy, SPARTAStrategy):
+        if isinstance(strategy, (SPARTAStrategy, SPARTADiLoCoStrategy)):
             return True
         if isinstance(strategy, FedAvgStrategy):
             return True
@@ -147,8 +150,8 @@ class ReplicaRunner:
                                        placement=s.placement_opt, **kw)
             else:
                 self.optim = _PerNodeOptim(spec, models, self.ra.arenas)
-            if isinstance(s, DiLoCoStrategy):
-                self.max_norm = s.kwargs.get("max_norm")
+            self.max_norm = s.kwargs.get("max_norm") if isinstance(s, DiLoCoStrategy) else s.max_norm
+            if isinstance(s, (DiLoCoStrategy, SPARTADiLoCoStrategy)):
                 hp = fused_sgd_hparams(s.outer_optim_spec)
                 if hp is not None:
                     self.outer = DiLoCoOuter(self.coll, self.K, ld, dev, dt, placement=s.placement_opt, **hp)
@@ -162,8 +165,6 @@ class ReplicaRunner:
                     self.master = torch.nn.Parameter(self.ra.flat_set[0].detach().float().clone())
                     self.outer_optimizer = s.outer_optim_spec.build([self.master])
                     self._avg = torch.empty(ld, device=dev, dtype=dt)
-            else:
-                self.max_norm = s.max_norm
             self.islands = (isinstance(s, FedAvgStrategy) and s.island_size is not None
                             and s.island_size < num_nodes)
             if isinstance(s, (SimpleReduceStrategy, FedAvgStrategy)) and not self.islands:
@@ -175,7 +176,7 @@ class ReplicaRunner:
             if self.islands:
                 self._isl_row = torch.empty(1, ld, device=dev, dtype=dt)
                 self._isl_all = None  # [num_nodes, ld]: every node's parameters, gathered (processes > 1)
-            elif isinstance(s, SPARTAStrategy):
+            elif isinstance(s, (SPARTAStrategy, SPARTADiLoCoStrategy)):
                 self.sparta = Sparta(self.coll, self.K, ld, dev, dt, s.index_selector.p)
                 sel = s.index_selector
                 self.philox = isinstance(sel, RandomIndexSelector) and sel.mask_source == "philox"
@@ -188,6 +189,14 @@ class ReplicaRunner:
                     self.bits = torch.zeros(ops.sparta_mask_words(ld), dtype=torch.int64, device=dev)
                     self.draw = MaskDraw()
                 self.iteration = 0
+            if isinstance(s, SPARTADiLoCoStrategy):
+                # a boundary step as one pass: needs the mask as packed words in memory, every node in
+                # this process, and the fused outer engine
+                self.fuse = bool(s.fuse_boundary and not self.philox and not self.coll.exchange
+                                 and isinstance(self.outer, DiLoCoOuter))
+                s.fuse_boundary = self.fuse
+                if isinstance(self.outer, DiLoCoOuter):
+                    s.engine = self.outer  # Strategy.placement_records reads the outer step's record there
         # the strategy's LR schedule on every optimizer (strategy.py:75-112)
         for o in (self.optim.opts if isinstance(self.optim, _PerNodeOptim) else [self.optim]):
             s.optim = o
@@ -221,13 +230,18 @@ class ReplicaRunner:
                 self.outer(P)
         elif isinstance(s, SPARTAStrategy):
             self._inner()
-            if self.philox:
-                self.sparta(P, seed=self.seed, iteration=self.iteration, skip=self._skip_table())
+            self._sparse_average(P)
+            self.iteration += 1
+        elif isinstance(s, SPARTADiLoCoStrategy):
+            self._inner()
+            boundary = s.local_step % s.H == 0 and s.local_step > 0
+            if boundary and self.fuse:
+                self.outer(P, sparse_mask=self._boundary_bits())
             else:
-                sel = s.index_selector
-                m = self._build_mask()
-                self.sparta(P, mask=m, mask_cap=self.sparta.cap if type(sel) is RandomIndexSelector else None,
-                            mask_shared=self.mask_shared)
+                self._sparse_average(P)
+                if boundary:
+                    self.outer(P)
+            s.mask_draw = "philox" if self.philox else self.draw.mode
             self.iteration += 1
         elif isinstance(s, FedAvgStrategy):
             self._inner()
@@ -344,6 +358,27 @@ class ReplicaRunner:
                             self.iteration, self.draw, bits=self.bits, coll=self.coll, defer=True)
         self.mask_shared = packed is not None
         return self.mask if packed is None else packed
+
+    def _sparse_average(self, P):
+        s = self.s
+        if self.philox:
+            self.sparta(P, seed=self.seed, iteration=self.iteration, skip=self._skip_table())
+        else:
+            sel = s.index_selector
+            m = self._build_mask()
+            self.sparta(P, mask=m, mask_cap=self.sparta.cap if type(sel) is RandomIndexSelector else None,
+                        mask_shared=self.mask_shared)
+
+    def _boundary_bits(self):
+        """This step's mask as packed words for the one-pass boundary step: the
+        draw of _build_mask made now instead of inside the SPARTA kernel (the same
+        bits, the generator advanced the same way), or the byte arena packed."""
+        a0 = self.ra.arenas[0]
+        packed = draw_masks(self.s.index_selector, a0.params, self.ra.layout.views(self.mask), set(self._grad_less()),
+                            self.iteration, self.draw, bits=self.bits, coll=self.coll, defer=False)
+        if packed is None:
+            ops.sparta_pack_mask(self.mask, self.mask.numel(), self.bits)
+        return self.bits
 
     def _inner(self):
         if isinstance(self.optim, ArenaAdam):

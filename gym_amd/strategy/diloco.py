@@ -20,6 +20,7 @@ import torch
 
 from .. import ops
 from ..engine import DiLoCoOuter
+from .communicate_optimize_strategy import CommunicationModule
 from .optim import OptimSpec, ensure_optim_spec
 from .strategy import Strategy, build_inner_optimizer, clip_and_step
 
@@ -44,12 +45,63 @@ def fused_sgd_hparams(spec: OptimSpec):
     return hp
 
 
+def default_outer_spec():
+    return OptimSpec(torch.optim.SGD, lr=0.7, nesterov=True, momentum=0.9)
+
+
+class DiLoCoCommunicator(CommunicationModule):
+    """DiLoCo's outer step as a communication module of a
+    CommunicateOptimizeStrategy (the name sparta_diloco.py:6 imports): every H
+    steps (local_step % H == 0 and local_step > 0, diloco.py:62) the outer
+    optimizer steps a master copy on master - average and every node takes the
+    master.  The same engines as DiLoCoStrategy: the fused kernel for an
+    SGD-family outer spec, torch's optimizer on an fp32 master otherwise."""
+
+    def __init__(self, H: int = 100, outer_optim: Optional[Union[str, OptimSpec]] = None, **kwargs):
+        super().__init__(**kwargs)
+        self.H = H
+        self.outer_optim_spec = ensure_optim_spec(outer_optim, default_outer_spec())
+        self._engine = None
+        self.outer_optimizer = None
+
+    def _init_node(self, model, rank, num_nodes):
+        s = self.strategy
+        arena = s.arena
+        # the reference's master copy is rank 0's initial model (diloco.py:81-82)
+        s.coll.broadcast_(arena.flat, 0)
+        hp = fused_sgd_hparams(self.outer_optim_spec)
+        if hp is not None:
+            self._engine = DiLoCoOuter(s.coll, 1, arena.n, arena.device, arena.dtype, placement=s.placement_opt, **hp)
+            self._engine.init_master(arena.flat)
+            s.engine = self._engine  # Strategy.placement_records reads the outer step's record there
+        else:
+            self.master = torch.nn.Parameter(arena.flat.detach().float().clone())
+            self.outer_optimizer = self.outer_optim_spec.build([self.master])
+            self._avg = torch.empty_like(arena.flat)
+
+    def communicate(self, model, rank: int, num_nodes: int, local_step: int) -> None:
+        if not (local_step % self.H == 0 and local_step > 0):
+            return
+        s = self.strategy
+        s.arena.check_bound()
+        if self._engine is not None:
+            self._engine(s.arena.flat.view(1, -1))
+            return
+        self._avg.copy_(s.arena.flat)
+        s.coll.all_reduce_(self._avg)
+        ops.replica_mean(self._avg, self._avg, divisor=s.coll.world)
+        self.outer_optimizer.zero_grad()
+        self.master.grad = self.master.detach() - self._avg.float()
+        self.outer_optimizer.step()
+        with torch.no_grad():
+            s.arena.flat.copy_(self.master)
+
+
 class DiLoCoStrategy(Strategy):
     def __init__(self, optim_spec: Optional[Union[str, OptimSpec]] = None,
                  outer_optim_spec: Optional[Union[str, OptimSpec]] = None, H: int = 100, **kwargs):
         self.inner_optim_spec = ensure_optim_spec(optim_spec, OptimSpec(torch.optim.AdamW))
-        self.outer_optim_spec = ensure_optim_spec(
-            outer_optim_spec, OptimSpec(torch.optim.SGD, lr=0.7, nesterov=True, momentum=0.9))
+        self.outer_optim_spec = ensure_optim_spec(outer_optim_spec, default_outer_spec())
         self.H = H
         super().__init__(**kwargs)
 

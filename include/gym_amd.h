@@ -208,6 +208,29 @@ GA_API int ga_diloco_outer(int dtype, const void* src, int64_t K, int64_t ld_src
                            float dampening, float weight_decay, int nesterov,
                            void* dst, int64_t K_out, int64_t ld_dst, hipStream_t stream);
 
+/*
+ * SPARTA's sparse average and the outer step that follows it on a DiLoCo
+ * boundary step (SPARTA+DiLoCo: sparta_diloco.py), as the outer step's one pass.
+ * `bits` are the packed mask words of ga_sparta_pack_mask / ga_sparta_torch_bernoulli
+ * (GA_MASK_BITS), ceil(n / 64) of them.  An element whose bit is clear is
+ * ga_diloco_outer's; a selected one takes the arithmetic of
+ * ga_sparta_average_local followed by ga_diloco_outer:
+ *   s  = sum_{k<K} src_k[i]                      (fp32, ascending k)
+ *   a  = s / sparse_divisor, rounded to `dtype`  (what SPARTA stores in every row)
+ *   s' = a + a + ... (K fp32 additions from 0)   (what the outer step then sums)
+ * and the update above on s'.  Bit-identical to the two launches.  Valid only
+ * where the outer step overwrites every row the average wrote: dst == src,
+ * K_out == K, ld_dst == ld_src, else GA_EINVAL.  master and mom are fp32
+ * (master_f32 != 0 for a bf16 set).  Algorithmic bytes (2K + 4) * 4 n + n / 8
+ * for fp32.
+ */
+GA_API int ga_diloco_outer_masked(int dtype, void* src, int64_t K, int64_t ld_src, int64_t n,
+                                  const uint64_t* bits, float sparse_divisor, float divisor,
+                                  void* master, void* mom, int master_f32, int first_step,
+                                  float lr, float momentum, float dampening, float weight_decay,
+                                  int nesterov, void* dst, int64_t K_out, int64_t ld_dst,
+                                  hipStream_t stream);
+
 /* ---- SPARTA sparse averaging ------------------------------------------- */
 
 /* Workspace bytes needed by ga_sparta_select for an arena of n elements. */
