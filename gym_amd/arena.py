@@ -143,9 +143,13 @@ class ParamArena:
                                "update parameters in place (param.data.copy_) instead")
 
     def sync_grads(self):
-        """Make sure every .grad is the arena view (autograd allocates a fresh
-        tensor when .grad was None, e.g. after zero_grad(set_to_none=True)):
-        copy such grads into the arena and re-point them."""
+        """Make sure every .grad that exists is the arena view (autograd
+        allocates a fresh tensor when .grad was None, e.g. after
+        zero_grad(set_to_none=True)): copy such grads into the arena and
+        re-point them.  A parameter without a gradient keeps .grad None, so the
+        optimizer and SPARTA skip it as the reference does; its span of the
+        arena is zeroed, so whole-arena norms and means stay correct.  The next
+        zero_grad() binds it to the arena again."""
         if self._grad_views is None:
             return
         for p, g in zip(self.params, self._grad_views):
@@ -156,7 +160,8 @@ class ParamArena:
                 continue
             if cur is None:
                 g.zero_()
-            elif cur.data_ptr() != g.data_ptr():
+                continue
+            if cur.data_ptr() != g.data_ptr():
                 g.copy_(cur)
             p.grad = g
 

@@ -11,11 +11,22 @@ with clipping, one norm reduction (ga_grad_clip_coef) whose coefficient the
 step kernel applies on the device -- no host synchronisation.
 
 Exactness: parameters whose .grad is None at step time are skipped, as torch
-does (the kernel runs over the contiguous arena ranges that have gradients).
-The per-parameter state (exp_avg, exp_avg_sq, step) are views of the flat
-state buffers, so state_dict() has torch's layout, and load_state_dict()
-(of an ArenaAdam or a torch.optim.Adam/AdamW state dict) copies the loaded
-moments into those buffers, so a resumed run continues where it stopped.
+does: no decay, no moment update, and the parameter's own `step` does not
+advance.  torch keeps one `step` per parameter and so does ArenaAdam: while
+every parameter has had a gradient on every step they all share one count
+tensor (one launch over the whole [K, ld] set, nothing kept per parameter);
+when some parameter is absent the parameters fall into groups that share a
+count (a group advances with one add, splits when only part of it is present,
+and groups that meet on a count merge again), and the kernel runs once per
+contiguous arena range whose parameters are present and share a count
+(step_size and bc2_sqrt, the bias corrections, are scalars of a launch).  A step on which no parameter has a
+gradient launches nothing.  exp_avg / exp_avg_sq of the per-parameter state
+are views of the flat state buffers, so state_dict() has torch's layout and
+values (a parameter that never had a gradient reports step 0 and zero moments,
+where torch has no entry), and load_state_dict() (of an ArenaAdam or a
+torch.optim.Adam/AdamW state dict, with equal or different per-parameter
+steps) copies the loaded moments into those buffers, so a resumed run
+continues where it stopped.
 """
 import math
 import time
@@ -147,7 +158,10 @@ class ArenaAdam(torch.optim.Optimizer):
         # placement) each in its own candidate buffer, when _M / _V are None
         self._Mr, self._Vr = list(self._M.unbind(0)), list(self._V.unbind(0))
         self.exp_avg, self.exp_avg_sq = self._M.view(-1), self._V.view(-1)  # flat views (single-arena users)
-        self._step_t = torch.tensor(0.0)
+        # the step counts: [count tensor, [(param, replica, offset, numel)]] per group of parameters that
+        # share a count -- state[p]["step"] of its members IS the group's tensor, so a step advances a
+        # group with one add.  One group while every parameter has had a gradient on every step.
+        self._groups = [[torch.tensor(0.0), []]]
         where = {}
         for k, ar in enumerate(self.arenas):
             for i, p in enumerate(ar.params):
@@ -159,6 +173,7 @@ class ArenaAdam(torch.optim.Optimizer):
                 raise ValueError("ArenaAdam: every parameter must live in the arena")
             k, o, n = where[id(p)]
             self._spans[k].append((p, o, n))
+            self._groups[0][1].append((p, k, o, n))
             self._bind_state(p)
         for sp in self._spans:
             sp.sort(key=lambda t: t[1])
@@ -193,16 +208,27 @@ class ArenaAdam(torch.optim.Optimizer):
 
     def _bind_state(self, p):
         k, o, n = self._where[id(p)]
-        self.state[p] = {"step": self._step_t, "exp_avg": self._Mr[k][o:o + n].view(p.shape),
+        st = self.state.get(p)
+        step = st["step"] if st else self._groups[0][0]  # its group's count tensor
+        self.state[p] = {"step": step, "exp_avg": self._Mr[k][o:o + n].view(p.shape),
                          "exp_avg_sq": self._Vr[k][o:o + n].view(p.shape)}
+
+    def state_dict(self):
+        """torch's layout, every parameter with a `step` tensor of its own (here
+        the parameters of a group share one; torch's optimizers, which advance
+        each entry in place, must not)."""
+        sd = super().state_dict()
+        sd["state"] = {i: {**st, "step": st["step"].clone()} for i, st in sd["state"].items()}
+        return sd
 
     def load_state_dict(self, state_dict):
         """torch's Optimizer.load_state_dict, then the loaded per-parameter
         moments are copied into the flat state buffers the kernel reads and the
-        state is re-pointed at those views.  The kernel keeps one step count
-        for the arena, so every parameter must carry the same `step`."""
+        state is re-pointed at those views.  Parameters may carry different
+        `step` counts (torch's do once one of them missed a gradient); one
+        without an entry starts at step 0 with zero moments."""
         super().load_state_dict(state_dict)
-        steps = set()
+        steps = {}
         with torch.no_grad():
             for r in self._Mr + self._Vr:
                 r.zero_()
@@ -212,14 +238,16 @@ class ArenaAdam(torch.optim.Optimizer):
                 if "exp_avg" in st:
                     self._Mr[k][o:o + n].copy_(st["exp_avg"].reshape(-1))
                     self._Vr[k][o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
-                if "step" in st:
-                    steps.add(float(st["step"]))
-        if len(steps) > 1:
-            raise ValueError(f"ArenaAdam: parameters carry different step counts {sorted(steps)}; "
-                             "the fused step keeps one count per arena")
-        self._step_t = torch.tensor(steps.pop() if steps else 0.0)
-        for p in self.param_groups[0]["params"]:
-            self._bind_state(p)
+                steps[id(p)] = float(st["step"]) if "step" in st else 0.0
+        groups = {}  # one group, and one count tensor, per distinct count
+        for k, sp in enumerate(self._spans):
+            for p, o, n in sp:
+                t = steps[id(p)]
+                g = groups.get(t) or groups.setdefault(t, [torch.tensor(t), []])
+                g[1].append((p, k, o, n))
+                self.state[p]["step"] = g[0]
+                self._bind_state(p)
+        self._groups = list(groups.values())
 
     def _place(self):
         """Choose the physical memory of the moments, once, before the first
@@ -273,15 +301,24 @@ class ArenaAdam(torch.optim.Optimizer):
         chosen = 0
         if best is not None:
             chosen = min(range(len(times)), key=lambda i: times[i])
-            M, V = split(best)
-            M.copy_(self._M)
-            V.copy_(self._V)
-            self._M, self._V, self._placed = M, V, best
-            self._Mr, self._Vr = list(M.unbind(0)), list(V.unbind(0))
-            self.exp_avg, self.exp_avg_sq = M.view(-1), V.view(-1)
-            for p in self.param_groups[0]["params"]:
-                self._bind_state(p)
+            self.move_moments(*split(best), owner=best)
         self.placement = {"candidates": len(times), "probe_ms": [round(t, 4) for t in times], "chosen": chosen}
+
+    def move_moments(self, M, V, owner=None):
+        """Move exp_avg / exp_avg_sq into other [K, ld] fp32 buffers (contents
+        copied, the per-parameter state re-pointed); `owner` keeps their memory
+        alive.  The placement search's move, also open to a caller that wants
+        the moments in memory of its own."""
+        if M.shape != self.P.shape or V.shape != self.P.shape or M.dtype != torch.float32 or V.dtype != torch.float32:
+            raise ValueError("ArenaAdam.move_moments: [K, ld] float32 buffers")
+        with torch.no_grad():
+            M.copy_(self.M)
+            V.copy_(self.V)
+        self._M, self._V, self._placed = M, V, owner
+        self._Mr, self._Vr = list(M.unbind(0)), list(V.unbind(0))
+        self.exp_avg, self.exp_avg_sq = M.view(-1), V.view(-1)
+        for p in self.param_groups[0]["params"]:
+            self._bind_state(p)
 
     def _place_rows(self, placement):
         Mr, Vr, bufs, rec = place_moment_rows(self.P, self.G, self._Mr, self._Vr)
@@ -294,50 +331,89 @@ class ArenaAdam(torch.optim.Optimizer):
             torch.cuda.empty_cache()
         self.placement = rec
 
-    def _ranges(self, k):
-        """Contiguous ranges [a, b) of replica k's arena whose parameters have a
-        gradient now (the whole row when all do: the padding stays 0)."""
-        live = [(o, n) for p, o, n in self._spans[k] if p.grad is not None]
-        if len(live) == len(self._spans[k]):
-            return [(0, self.ld)]
-        out = []
-        for o, n in live:
-            if out and o - out[-1][1] < 64:  # adjacent tensors (the alignment gap is zero padding)
-                out[-1][1] = o + n
-            else:
-                out.append([o, o + n])
-        return [(a, b) for a, b in out]
-
     @torch.no_grad()
     def step(self, closure=None, max_norm=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        ranges = [self._ranges(k) for k in range(self.K)]
+        ranges = self._advance()
         for ar in self.arenas:
             ar.sync_grads()
+        if not any(ranges):  # no parameter has a gradient: torch's step does nothing
+            return loss
         if self._placed_for != (self.P.data_ptr(), self.G.data_ptr()):
             self._place()
-        g = self.param_groups[0]
-        lr, (b1, b2), eps, wd = float(g["lr"]), g["betas"], float(g["eps"]), float(g["weight_decay"])
-        decoupled = g["decoupled_weight_decay"]
-        self._step_t += 1
-        t = float(self._step_t)
-        bc1 = 1 - b1 ** t
-        bc2 = 1 - b2 ** t
-        hp = dict(lerp_w=1 - b1, beta2=b2, one_m_beta2=1 - b2, eps=eps,
-                  wd_factor=(1 - lr * wd) if (decoupled and wd != 0) else 1.0,
-                  l2_wd=wd if (not decoupled and wd != 0) else 0.0, step_size=-(lr / bc1), bc2_sqrt=math.sqrt(bc2))
         clip = None
         if max_norm:
             ops.grad_clip_coef(self.G, self.ld, max_norm, self._partials, self._clip)
             clip = self._clip
-        if self._M is not None and all(r == [(0, self.ld)] for r in ranges):
-            ops.adam_step(self.P, self.G, self._M, self._V, clip_coef=clip, **hp)
+        whole = ranges[0]
+        if self._M is not None and whole and whole[0][:2] == (0, self.ld) and all(r == whole for r in ranges):
+            ops.adam_step(self.P, self.G, self._M, self._V, clip_coef=clip, **self._hp(whole[0][2]))
             return loss
-        for k in range(self.K):  # per replica (its moments placed apart, or partial ranges)
+        hps = {}
+        for k in range(self.K):  # per replica (its moments placed apart, partial ranges, or counts apart)
             ck = clip[2 * k:2 * k + 2] if clip is not None else None
-            for a, b in ranges[k]:
+            for a, b, t in ranges[k]:
+                hp = hps.get(t) or hps.setdefault(t, self._hp(t))
                 ops.adam_step(self.P[k, a:b], self.G[k, a:b], self._Mr[k][a:b], self._Vr[k][a:b], clip_coef=ck, **hp)
         return loss
+
+    def _advance(self):
+        """Advance the count of every parameter that has a gradient now and
+        return, per replica, [(a, b, t)]: the contiguous ranges of present
+        parameters that share the count t (the whole row when all of a replica
+        are present on one count: the padding stays 0).  A group whose members
+        are all present advances with one add; one that is partly present
+        splits; groups that reach the same count become one again."""
+        groups = self._groups
+        if len(groups) == 1 and all(m[0].grad is not None for m in groups[0][1]):
+            groups[0][0] += 1  # every parameter present on one count: nothing per parameter
+            return [[(0, self.ld, float(groups[0][0]))]] * self.K
+        live = [[] for _ in range(self.K)]
+        merged = {}  # count -> [its tensor, members]
+        for clock, members in groups:
+            here = [m for m in members if m[0].grad is not None]
+            if len(here) == len(members):
+                clock += 1
+                parts = [(clock, members)]
+            elif not here:
+                parts = [(clock, members)]
+            else:  # the present members go on with a count tensor of their own
+                parts = [(clock, [m for m in members if m[0].grad is None]), (clock + 1, here)]
+            if here:
+                t = float(parts[-1][0])
+                for _, k, o, n in here:
+                    live[k].append((o, n, t))
+            for c, ms in parts:
+                into = merged.setdefault(float(c), [c, []])
+                into[1].extend(ms)
+                if into[0] is not clock:
+                    for m in ms:
+                        self.state[m[0]]["step"] = into[0]
+        self._groups = list(merged.values())
+        ranges = []
+        for k, spans in enumerate(live):
+            spans.sort()
+            out = []
+            for o, n, t in spans:
+                if out and o - out[-1][1] < 64 and out[-1][2] == t:  # adjacent (zero padding between), same count
+                    out[-1][1] = o + n
+                else:
+                    out.append([o, o + n, t])
+            if len(out) == 1 and len(spans) == len(self._spans[k]):
+                out = [[0, self.ld, out[0][2]]]
+            ranges.append([tuple(r) for r in out])
+        return ranges
+
+    def _hp(self, t):
+        """The launch scalars of a step at count t (torch's _single_tensor_adam)."""
+        g = self.param_groups[0]
+        lr, (b1, b2), eps, wd = float(g["lr"]), g["betas"], float(g["eps"]), float(g["weight_decay"])
+        decoupled = g["decoupled_weight_decay"]
+        bc1 = 1 - b1 ** t
+        bc2 = 1 - b2 ** t
+        return dict(lerp_w=1 - b1, beta2=b2, one_m_beta2=1 - b2, eps=eps,
+                    wd_factor=(1 - lr * wd) if (decoupled and wd != 0) else 1.0,
+                    l2_wd=wd if (not decoupled and wd != 0) else 0.0, step_size=-(lr / bc1), bc2_sqrt=math.sqrt(bc2))

@@ -520,6 +520,7 @@ class BatchedForward:
         m0 = self.models[0]
         self.names = [n for n, _ in m0.named_parameters()]
         self.trainable = [p.requires_grad for p in m0.parameters()]
+        self.reached = set()  # indices of the parameters backward accumulated a gradient into (the caller clears it)
         if len(self.names) != len(ra.layout.shapes):
             raise ValueError("BatchedForward: the model's parameters do not match the arena layout")
         self.buf_names = [n for n, _ in m0.named_buffers()]
@@ -538,11 +539,12 @@ class BatchedForward:
         ra, L = self.ra, self.ra.layout
         P, G = ra.flat_set, ra.grad_set
         leaves = []
-        for o, n, shape, train in zip(L.offsets, L.numels, L.shapes, self.trainable):
+        for i, (o, n, shape, train) in enumerate(zip(L.offsets, L.numels, L.shapes, self.trainable)):
             w = P[c0:c1, o:o + n].view(c1 - c0, *shape).detach()
             if train:
                 w.requires_grad_(True)
                 w.grad = G[c0:c1, o:o + n].view(c1 - c0, *shape)
+                w.register_post_accumulate_grad_hook(lambda _, i=i: self.reached.add(i))
             leaves.append(w)
         return leaves
 
@@ -581,7 +583,7 @@ class ReplicaTrainNode:
                  max_steps=None, batch_size=16, minibatch_size=16, val_size=64, val_interval=100, shuffle=True,
                  autocast=False, replica_forward="loop", replica_vmap_chunk=None, correlation_interval=None,
                  drift_detail=False, **kwargs):
-        from .train_node import RunLog
+        from .train_node import RunLog, watch_reached
         seed = kwargs.get("seed", 42)
         torch.manual_seed(seed)
         torch.cuda.manual_seed(seed)
@@ -612,6 +614,8 @@ class ReplicaTrainNode:
             raise ValueError(f"replica_forward must be 'loop' or 'vmap', got {replica_forward!r}")
         self.batched = (BatchedForward(self.models, self.runner.ra, replica_vmap_chunk)
                         if replica_forward == "vmap" else None)
+        # the loop forward's record of the parameters backward reached (the vmap forward keeps its own)
+        self._reached = watch_reached(p for m in self.models for p in m.parameters()) if self.batched is None else None
         if max_steps is None:
             max_steps = num_epochs * len(self.loaders[0]) / (batch_size // minibatch_size)
         self.max_steps = max_steps
@@ -658,16 +662,26 @@ class ReplicaTrainNode:
         self.runner.zero_grad()
         accum = self.batch_size // self.minibatch_size
         loss0 = None
+        # parameters backward does not reach get .grad = None, the reference's state at
+        # strategy.step() (train_node.drop_unreached); the next zero_grad() binds them again
         if self.batched is not None:
+            self.batched.reached.clear()
             for _ in range(accum):  # each node's loader in node order, as the loop draws them
                 loss0 = self.batched([self._next(k) for k in range(self.K)], self._autocast)[0]
+            for m in self.models:
+                for i, p in enumerate(m.parameters()):
+                    if p.requires_grad and i not in self.batched.reached:
+                        p.grad = None
         else:
+            from .train_node import drop_unreached
+            self._reached.clear()
             for k, m in enumerate(self.models):
                 for _ in range(accum):
                     loss = self._forward(m, self._next(k))
                     loss.backward()
                     if k == 0:
                         loss0 = loss
+                drop_unreached(m.parameters(), self._reached)
         self.runner.ra.sync_grads()
         self.runner.ra.grad_set.div_(self.batch_size / self.minibatch_size)
         self.runner.step()

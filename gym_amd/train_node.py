@@ -61,6 +61,32 @@ class RunLog:
                 "metrics": list(self.metrics)}
 
 
+def watch_reached(params):
+    """A set that autograd fills with the trainable parameters it accumulates a
+    gradient into (a post-accumulate-grad hook on each: it fires with a .grad
+    bound beforehand too).  The strategies' zero_grad() zeroes the gradient
+    arena and keeps every .grad bound to it, so after backward a parameter the
+    loss did not depend on holds zeros where the reference holds None
+    (optim.zero_grad() sets None and autograd never fills it); the train step
+    clears the set after zero_grad() and, after backward, drop_unreached()
+    restores None for the rest."""
+    reached = set()
+    for p in params:
+        if p.requires_grad:
+            p.register_post_accumulate_grad_hook(reached.add)
+    return reached
+
+
+def drop_unreached(params, reached):
+    """.grad = None for the trainable parameters backward did not reach: the
+    state the reference is in at strategy.step(), which skips them in the
+    all-reduce (strategy.py:131), the optimizer (torch skips a None grad) and
+    SPARTA's average (sparta.py:29).  The next zero_grad() binds them again."""
+    for p in params:
+        if p.requires_grad and p not in reached:
+            p.grad = None
+
+
 class TrainNode(LogModule):
     def __init__(self, model: torch.nn.Module,
                  train_dataset: Union[torch.utils.data.Dataset, Callable[[int, int, bool], torch.utils.data.Dataset]],
@@ -111,6 +137,7 @@ class TrainNode(LogModule):
         self.epoch = 0
         self.logger = None
         self.drift = None  # NodeDrift, built at the first measurement (correlation_interval set)
+        self._reached = watch_reached(self.model.parameters())
 
     def build_dataloaders(self):
         self.train_dataloader = DataLoader(self.train_dataset, batch_size=self.minibatch_size,
@@ -145,11 +172,13 @@ class TrainNode(LogModule):
 
     def _train_step(self):
         self.strategy.zero_grad()
+        self._reached.clear()
         accum = self.batch_size // self.minibatch_size
         loss = None
         for _ in range(accum):
             loss = self._forward(self.model, self._get_batch())
             loss.backward()
+        drop_unreached(self.model.parameters(), self._reached)
         for p in self.model.parameters():
             if p.requires_grad and p.grad is not None:
                 p.grad /= self.batch_size / self.minibatch_size

@@ -423,10 +423,59 @@ def gen_g5():
     np.savez_compressed(os.path.join(OUT, "lr_schedule.npz"), **out[0])
 
 
+# ---------------------------------------------------------------- G6 --------
+# Parameters without a gradient: the reference's SimpleReduce (AdamW, max_norm 1) and
+# DiLoCo (H = 2) on tests/tiny_models.GatedMLP, 2 nodes over gloo, 6 steps, with the
+# model, data and hyper-parameters of tests/absent_scenarios.py (zero_grad() -> None,
+# backward, step()).  Recorded: every node's parameters and per-parameter AdamW steps.
+def g6_worker(rank, world, port, q):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    import absent_scenarios as A
+    from exogym.strategy import DiLoCoStrategy, OptimSpec
+    from exogym.strategy.strategy import SimpleReduceStrategy
+    init(rank, world, port)
+    rec = {}
+    for name in ("simple", "diloco"):
+        model = A.model()
+        inner = OptimSpec(torch.optim.AdamW, lr=A.LR)
+        if name == "simple":
+            strat = SimpleReduceStrategy(optim_spec=inner, max_norm=A.MAX_NORM)
+        else:
+            strat = DiLoCoStrategy(optim_spec=inner, H=A.H)
+        strat._init_node(model, rank, world)
+        if name == "diloco":  # Q1: GPU semantics (the master is a copy), as in g2_worker
+            def sync_clone(self=strat):
+                for pname, param in self.model.named_parameters():
+                    param.data = self.master_model.state_dict()[pname].data.clone()
+            strat._synchronize_master_model = sync_clone
+        ds = A.node_data(rank)
+        for t in range(A.STEPS):
+            strat.zero_grad()
+            model(ds[t * A.BATCH:(t + 1) * A.BATCH]).backward()
+            strat.step()
+        params = list(model.parameters())
+        rec[f"{name}_params"] = [p.detach().numpy().copy() for p in params]
+        rec[f"{name}_steps"] = np.array([float(strat.optim.state[p]["step"]) if p in strat.optim.state else 0.0
+                                         for p in params])
+    q.put((rank, rec))
+    dist.destroy_process_group()
+
+
+def gen_g6():
+    out = run_spawn(g6_worker, 2)
+    res = {}
+    for name in ("simple", "diloco"):
+        for r in range(2):
+            res[f"{name}_steps_{r}"] = out[r][f"{name}_steps"]
+            for i, p in enumerate(out[r][f"{name}_params"]):
+                res[f"{name}_node{r}_{i}"] = p
+    np.savez_compressed(os.path.join(OUT, "absent_grads.npz"), **res)
+
+
 if __name__ == "__main__":
     torch.set_num_threads(1)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g3b", "g4c", "g4s", "g4b", "g5"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g3b", "g4c", "g4s", "g4b", "g5", "g6"]
     for w in which:
         {"g1": gen_g1, "g2": gen_g2, "g3": gen_g3, "g3b": gen_g3b, "g4c": gen_g4_codec,
-         "g4s": gen_g4_steps, "g4b": gen_g4_bf16, "g5": gen_g5}[w]()
+         "g4s": gen_g4_steps, "g4b": gen_g4_bf16, "g5": gen_g5, "g6": gen_g6}[w]()
         print("wrote", w, flush=True)

@@ -17,10 +17,199 @@ def fake(monkeypatch):
     return fake_ops
 
 
-@pytest.mark.parametrize("name,cls,kw,max_norm,skip", C.CASES, ids=[c[0] for c in C.CASES])
-def test_arena_adam_host_logic(fake, name, cls, kw, max_norm, skip):
-    ours, ref = C.run_pair("cpu", cls, kw, max_norm=max_norm, skip=skip)
+def absent_spans_unchanged(snap):
+    """An observer for optim_cases.run_pair: over every step on which a parameter
+    is absent, its value and both moments stay bit-identical."""
+    def observe(when, step, ctx):
+        opt = ctx["opt"]
+        for k, (m, pat) in enumerate(zip(ctx["models"], ctx["pats"])):
+            for i, p in enumerate(m.parameters()):
+                if pat.present(i, step):
+                    continue
+                st = opt.state[p]
+                cur = [t.detach().clone() for t in (p, st["exp_avg"], st["exp_avg_sq"])]
+                if when == "before":
+                    snap[k, i] = cur
+                else:
+                    for name, x, y in zip(("param", "exp_avg", "exp_avg_sq"), snap.pop((k, i)), cur):
+                        assert torch.equal(x, y), f"step {step} replica {k} tensor {i}: absent, but its {name} moved"
+    return observe
+
+
+@pytest.mark.parametrize("name,cls,kw,max_norm,skip,pattern", C.CASES, ids=[c[0] for c in C.CASES])
+def test_arena_adam_host_logic(fake, name, cls, kw, max_norm, skip, pattern):
+    """Parameters, exp_avg, exp_avg_sq within fp32 rounding of torch's and every
+    parameter's `step` exactly torch's; absent tensors untouched on their steps."""
+    ours, ref = C.run_pair("cpu", cls, kw, max_norm=max_norm, skip=skip, pattern=pattern, steps=C.case_steps(pattern),
+                           observe=absent_spans_unchanged({}))
     C.assert_close(ours, ref)
+
+
+@pytest.mark.parametrize("name,cls,kw,max_norm", C.REPLICA_CASES, ids=[c[0] for c in C.REPLICA_CASES])
+def test_arena_adam_replicas_host_logic(fake, name, cls, kw, max_norm):
+    """K = 3 rows of a ReplicaArena, a different presence pattern on each, against
+    three independent torch optimizers."""
+    ours, ref = C.run_pair("cpu", cls, kw, max_norm=max_norm, pattern=C.REPLICA_PATTERNS, K=3, steps=C.PATTERN_STEPS,
+                           observe=absent_spans_unchanged({}))
+    C.assert_close(ours, ref)
+
+
+def _record_launches(fake, monkeypatch):
+    """Wrap the stand-in's adam_step: calls[i] = (the parameter tensor it was
+    launched over, step_size, the clip buffer)."""
+    calls, real = [], fake.adam_step
+
+    def adam_step(param, grad, exp_avg, exp_avg_sq, **kw):
+        calls.append((param, kw["step_size"], kw.get("clip_coef")))
+        return real(param, grad, exp_avg, exp_avg_sq, **kw)
+
+    monkeypatch.setattr(fake, "adam_step", adam_step)
+    return calls
+
+
+def _step_size(lr, t, b1=0.9):
+    return -(lr / (1 - b1 ** float(t)))
+
+
+def test_all_present_is_one_launch_over_the_whole_set(fake, monkeypatch):
+    """Every parameter present on every step: one ga_adam_step call per step with
+    the full [K, ld] sets and the clip buffer whole (the path bench.py's
+    inner-optimizer leg times), K = 1 and K = 3."""
+    calls = _record_launches(fake, monkeypatch)
+    for K in (1, 3):
+        seen = {}
+
+        def observe(when, step, ctx):
+            if when == "before":
+                seen["n"] = len(calls)
+                return
+            opt = ctx["opt"]
+            assert len(calls) == seen["n"] + 1, f"step {step}: {len(calls) - seen['n']} launches"
+            param, step_size, clip = calls[-1]
+            assert param.data_ptr() == opt.P.data_ptr() and tuple(param.shape) == (K, opt.ld)
+            assert clip.data_ptr() == opt._clip.data_ptr() and clip.numel() == 2 * K
+            assert step_size == _step_size(1e-2, step + 1)
+            assert len(opt._groups) == 1  # one count for all: nothing per parameter was materialised
+
+        C.run_pair("cpu", torch.optim.AdamW, {"lr": 1e-2}, max_norm=0.5, pattern=[C.Pattern()] * K, K=K, steps=4,
+                   observe=observe)
+
+
+def test_gap_case_launches_exactly_the_expected_ranges(fake, monkeypatch):
+    """Tensor 1 absent at steps 2-3 (optim_cases "gap"): (replica, a, b,
+    step_size) of every launch.  Tensor offsets 0, 2112, 2240, 8384, 8448; the
+    last tensor ends at 8458."""
+    calls = _record_launches(fake, monkeypatch)
+    got = []
+
+    def observe(when, step, ctx):
+        if when == "after":
+            flat = ctx["arena"].flat
+            for param, step_size, _ in calls:
+                a = (param.data_ptr() - flat.data_ptr()) // 4
+                got.append((step, 0, a, a + param.numel(), step_size))
+            calls.clear()
+
+    C.run_pair("cpu", torch.optim.AdamW, {"lr": 1e-2}, pattern=dict(C.PATTERNS)["gap"], steps=6, observe=observe)
+    n, s = 8704, lambda t: _step_size(1e-2, t)
+    assert got == [(0, 0, 0, n, s(1)), (1, 0, 0, n, s(2)),
+                   (2, 0, 0, 2112, s(3)), (2, 0, 2240, 8458, s(3)),
+                   (3, 0, 0, 2112, s(4)), (3, 0, 2240, 8458, s(4)),
+                   (4, 0, 0, 2112, s(5)), (4, 0, 2112, 2240, s(3)), (4, 0, 2240, 8458, s(5)),
+                   (5, 0, 0, 2112, s(6)), (5, 0, 2112, 2240, s(4)), (5, 0, 2240, 8458, s(6))]
+
+
+def test_counts_that_meet_again_become_one_launch(fake, monkeypatch):
+    """Tensor 1 misses step 0 and the others miss step 1: every count is 1 again
+    after step 1, the groups merge, and steps 2-3 are the one launch over the
+    whole row.  A frozen tensor in the list keeps two groups (one add per step),
+    never one per parameter."""
+    calls = _record_launches(fake, monkeypatch)
+    shapes, groups = [], []
+
+    def observe(when, step, ctx):
+        if when == "after":
+            shapes.append([p.numel() for p, _, _ in calls])
+            groups.append(len(ctx["opt"]._groups))
+            calls.clear()
+
+    pat = C.Pattern({1: (0,), 0: (1,), 2: (1,), 3: (1,), 4: (1,)})
+    ours, ref = C.run_pair("cpu", torch.optim.AdamW, {"lr": 1e-2}, max_norm=0.5, pattern=pat, steps=4, observe=observe)
+    C.assert_close(ours, ref)
+    assert shapes == [[2112, 8458 - 2240], [128], [8704], [8704]] and groups == [2, 1, 1, 1]
+    del shapes[:], groups[:]
+    ours, ref = C.run_pair("cpu", torch.optim.AdamW, {"lr": 1e-2}, pattern=C.Pattern(frozen=(2,)), steps=3,
+                           observe=observe)
+    C.assert_close(ours, ref)
+    assert groups == [2, 2, 2] and shapes == [[2240, 8458 - 8384]] * 3
+
+
+def test_step_without_any_gradient_launches_nothing(fake, monkeypatch):
+    calls = _record_launches(fake, monkeypatch)
+    per_step = []
+
+    def observe(when, step, ctx):
+        if when == "after":
+            per_step.append(len(calls))
+            calls.clear()
+
+    ours, ref = C.run_pair("cpu", torch.optim.AdamW, {"lr": 1e-2}, max_norm=0.5, pattern=dict(C.PATTERNS)["empty-step"],
+                           steps=4, observe=observe)
+    assert per_step == [1, 1, 0, 1]
+    assert ours["step"] == ref["step"] == [3.0] * len(C.SHAPES)
+
+
+@pytest.mark.parametrize("direction", ["torch-to-arena", "arena-to-torch"])
+def test_state_round_trip_with_heterogeneous_steps(fake, direction):
+    """Four steps with tensor 1 late (absent at 0-1) and tensor 3 never present,
+    so the per-parameter steps are [4, 2, 4, 0, 4]; the state dict then moves to
+    the other optimizer, which continues two steps and must equal the first
+    continuing (torch has no entry for tensor 3; ArenaAdam reports step 0 and
+    zero moments for it)."""
+    import copy
+    from gym_amd.arena import ParamArena
+    from gym_amd.fused_optim import ArenaAdam
+    kw = {"lr": 1e-2, "weight_decay": 0.1}
+    pat = C.Pattern({1: (0, 1), 3: (0, 1, 2, 3)})
+
+    def drive(model, opt, steps, arena=None):
+        for step in steps:
+            if arena is not None:
+                arena.zero_grad()
+            for i, (p, g) in enumerate(zip(model.parameters(), C.grads_for(step))):
+                p.grad = g.clone() if pat.present(i, step) else None
+            if arena is not None:
+                opt.step(max_norm=0.5)
+            else:
+                torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.grad is not None], 0.5)
+                opt.step()
+
+    tm, am = C.make_model("cpu"), C.make_model("cpu")
+    arena = ParamArena(list(am.parameters()))
+    topt, aopt = torch.optim.AdamW(tm.parameters(), **kw), ArenaAdam(am.parameters(), arena, **kw)
+    drive(tm, topt, range(4))
+    drive(am, aopt, range(4), arena)
+    assert C._state(aopt, list(am.parameters()))["step"] == [4.0, 2.0, 4.0, 0.0, 4.0]
+    if direction == "torch-to-arena":
+        bm = C.make_model("cpu", seed=99)
+        with torch.no_grad():
+            for p, q in zip(bm.parameters(), tm.parameters()):
+                p.copy_(q)
+        barena = ParamArena(list(bm.parameters()))
+        bopt = ArenaAdam(bm.parameters(), barena, **kw)
+        bopt.load_state_dict(copy.deepcopy(topt.state_dict()))
+        assert C._state(bopt, list(bm.parameters()))["step"] == [4.0, 2.0, 4.0, 0.0, 4.0]
+        drive(bm, bopt, range(4, 6), barena)
+    else:
+        bm = C.make_model("cpu", seed=99)
+        with torch.no_grad():
+            for p, q in zip(bm.parameters(), am.parameters()):
+                p.copy_(q)
+        bopt = torch.optim.AdamW(bm.parameters(), **kw)
+        bopt.load_state_dict(copy.deepcopy(aopt.state_dict()))
+        drive(bm, bopt, range(4, 6))
+    drive(tm, topt, range(4, 6))
+    C.assert_close(C._state(bopt, list(bm.parameters())), C._state(topt, list(tm.parameters())))
 
 
 def test_oracle_adamw_pinned_to_torch():

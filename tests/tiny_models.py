@@ -16,6 +16,54 @@ class TinyMLP(torch.nn.Module):
         return torch.nn.functional.cross_entropy(self.fc2(torch.relu(self.fc1(x))), y)
 
 
+class GatedMLP(torch.nn.Module):
+    """Parameters that do not always get a gradient, gated on a count of
+    training-mode forwards (one per optimizer step without gradient
+    accumulation), so the pattern is the same on every node and every run:
+      fc1, fc2   used on every step
+      unused     trainable, never used: its .grad stays None in the reference
+      scale      frozen (requires_grad False), used on every step
+      late       used from the third step on (forwards 2, 3, ...)
+      gap        skipped on steps 2-3
+    present(name, step) tells which parameters step `step` reaches.  The count
+    follows optimizer steps only with one forward per step: not under gradient
+    accumulation, and not under the batched vmap forward with a chunk below K
+    (its one storage-free copy of the model counts a forward per chunk)."""
+
+    def __init__(self, d_in=32, d_hidden=24, n_cls=4):
+        super().__init__()
+        nn = torch.nn
+        self.fc1 = nn.Linear(d_in, d_hidden)
+        self.unused = nn.Parameter(torch.randn(5, 7) * 0.1)
+        self.scale = nn.Parameter(torch.rand(d_hidden) + 0.5, requires_grad=False)
+        self.late = nn.Linear(d_hidden, d_hidden)
+        self.gap = nn.Linear(d_hidden, d_hidden, bias=False)
+        self.fc2 = nn.Linear(d_hidden, n_cls)
+        self.forwards = 0
+
+    @staticmethod
+    def present(name, step):
+        if name == "unused" or name == "scale":
+            return False
+        if name.startswith("late."):
+            return step >= 2
+        if name.startswith("gap."):
+            return step not in (2, 3)
+        return True
+
+    def forward(self, batch):
+        x, y = batch
+        step = self.forwards
+        if self.training:
+            self.forwards += 1
+        h = torch.relu(self.fc1(x)) * self.scale
+        if not self.training or self.present("late.", step):
+            h = h + torch.tanh(self.late(h))
+        if not self.training or self.present("gap.", step):
+            h = h + torch.tanh(self.gap(h))
+        return torch.nn.functional.cross_entropy(self.fc2(h), y)
+
+
 def dataset(n=256, d_in=32, n_cls=4, seed=0):
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(n, d_in, generator=g)
