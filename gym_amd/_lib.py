@@ -92,6 +92,8 @@ SIGNATURES = {
     "ga_grad_clip_coef": (c_i32, [c_i32, c_p, c_i64, c_i64, c_i64, c_f32, c_p, c_p, c_p]),
     "ga_adam_step": (c_i32, [c_i32, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32,
                              c_f32, c_f32, c_f32, c_p, c_p]),
+    "ga_sgd_step": (c_i32, [c_i32, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32,
+                            c_p, c_p]),
     "ga_replica_gram_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "ga_replica_gram_chain": (c_i32, []),
     "ga_replica_gram": (c_i32, [c_i32, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p]),

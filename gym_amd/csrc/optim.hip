@@ -12,8 +12,14 @@
 //   p += step_size * m / (sqrt(v)/bc2_sqrt + eps),  step_size = -lr/(1-b1^t), bc2_sqrt = sqrt(1-b2^t)
 // 28 bytes per element (read p, g, m, v; write p, m, v), +4 when the clipped
 // gradient is written back.
+//
+// SGD (torch.optim.SGD: momentum, dampening, Nesterov, L2 weight decay) is the same
+// pass with fewer streams (sgd_math.h): 12 bytes per element without momentum (read
+// p, g; write p), 20 with (the momentum buffer read and written), 16 on a parameter's
+// first step (the buffer is only written), +4 when the clipped gradient is written back.
 #include "ga_common.h"
 #include "adam_math.h"
+#include "sgd_math.h"
 
 
 namespace ga {
@@ -66,6 +72,55 @@ __global__ __launch_bounds__(kOptBlock) void adam_kernel(float* __restrict__ par
             param[j] = p;
             m_[j] = m;
             v_[j] = v;
+        }
+    }
+}
+
+// SGD over the arena, adam_kernel's shape: replicas on grid.y, kOptChunk float4 per
+// workgroup, nt loads, sc1 stores.  kMomentum / kFirst / kNesterov are uniform over a
+// launch; without momentum the buffer pointer is never touched (it may be null), on a
+// first step it is written and not read.
+template <bool kMomentum, bool kFirst, bool kNesterov>
+__global__ __launch_bounds__(kOptBlock) void sgd_kernel(float* __restrict__ param, float* __restrict__ grad,
+                                                        float* __restrict__ buf_, int64_t n, int64_t ld,
+                                                        SgdParams sp, const float* __restrict__ clip_coef) {
+    const int64_t rep = blockIdx.y;
+    param += rep * ld;
+    grad += rep * ld;
+    if (kMomentum) buf_ += rep * ld;
+    const float coef = clip_coef ? clip_coef[2 * rep] : 1.f;
+    const bool scale = !(coef >= 1.f);  // a NaN coefficient scales too (ga_adam_step's rule)
+    const int64_t nv = n >> 2;
+    const int64_t lo = (int64_t)blockIdx.x * kOptChunk;
+    const int64_t hi = lo + kOptChunk < nv ? lo + kOptChunk : nv;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += kOptBlock) {
+        float4 p = stream_load(reinterpret_cast<const float4*>(param) + i);
+        float4 g = stream_load(reinterpret_cast<const float4*>(grad) + i);
+        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (kMomentum && !kFirst) b = stream_load(reinterpret_cast<const float4*>(buf_) + i);
+        if (scale) {
+            g.x *= coef; g.y *= coef; g.z *= coef; g.w *= coef;
+            stream_store(reinterpret_cast<float4*>(grad) + i, g);  // clip_grad_norm_ leaves the clipped grads
+        }
+        float pp[4] = {p.x, p.y, p.z, p.w}, gg[4] = {g.x, g.y, g.z, g.w}, bb[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sgd_elem<kMomentum, kFirst, kNesterov>(pp[e], gg[e], bb[e], sp);
+        const uint32_t o = (uint32_t)(i - lo);
+        store_sc1(reinterpret_cast<float4*>(param) + lo, o, make_float4(pp[0], pp[1], pp[2], pp[3]));
+        if (kMomentum) store_sc1(reinterpret_cast<float4*>(buf_) + lo, o, make_float4(bb[0], bb[1], bb[2], bb[3]));
+    }
+    // scalar tail (n % 4), handled by the last workgroup
+    if (blockIdx.x == gridDim.x - 1) {
+        for (int64_t j = (nv << 2) + threadIdx.x; j < n; j += kOptBlock) {
+            float p = param[j], g = grad[j], b = 0.f;
+            if (kMomentum && !kFirst) b = buf_[j];
+            if (scale) {
+                g *= coef;
+                grad[j] = g;
+            }
+            sgd_elem<kMomentum, kFirst, kNesterov>(p, g, b, sp);
+            param[j] = p;
+            if (kMomentum) buf_[j] = b;
         }
     }
 }
@@ -201,6 +256,35 @@ extern "C" GA_API int ga_adam_step(int dtype, void* param, void* grad, float* ex
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)grid, (unsigned)K), dim3(kOptBlock), 0, stream, (float*)param,
                        (float*)grad, exp_avg, exp_avg_sq, n, ld, ap, clip_coef);
     return check_launch("ga_adam_step");
+}
+
+extern "C" GA_API int ga_sgd_step(int dtype, void* param, void* grad, float* momentum_buf, int64_t K, int64_t ld,
+                                  int64_t n, float neg_lr, float momentum, float one_m_dampening, float weight_decay,
+                                  int nesterov, int first, const float* clip_coef, hipStream_t stream) {
+    clear_error();
+    GA_REQUIRE(n >= 0 && K >= 1 && K <= 65535, "ga_sgd_step: bad sizes n=%lld K=%lld", (long long)n, (long long)K);
+    if (n == 0) return GA_OK;
+    GA_REQUIRE(K == 1 || (ld >= n && ld % 4 == 0), "ga_sgd_step: ld must be >= n and a multiple of 4");
+    const bool mom = momentum != 0.f;
+    GA_REQUIRE(param && grad, "ga_sgd_step: null buffer");
+    GA_REQUIRE(!mom || momentum_buf, "ga_sgd_step: null momentum buffer with momentum %g", (double)momentum);
+    GA_REQUIRE(dtype == GA_F32, "ga_sgd_step: only float32 arenas are fused (dtype %d)", dtype);
+    GA_REQUIRE(((uintptr_t)param | (uintptr_t)grad | (mom ? (uintptr_t)momentum_buf : 0)) % 16 == 0,
+               "ga_sgd_step: buffers must be 16-byte aligned");
+    const SgdParams sp{neg_lr, momentum, one_m_dampening, weight_decay};
+    int64_t g = (n / 4 + kOptChunk - 1) / kOptChunk;
+    if (g < 1) g = 1;
+    const dim3 grid((unsigned)g, (unsigned)K), block(kOptBlock);
+    float *p = (float*)param, *gr = (float*)grad;
+#define GA_SGD_LAUNCH(M, F, N) \
+    hipLaunchKernelGGL((sgd_kernel<M, F, N>), grid, block, 0, stream, p, gr, momentum_buf, n, ld, sp, clip_coef)
+    if (!mom) GA_SGD_LAUNCH(false, false, false);
+    else if (first && nesterov) GA_SGD_LAUNCH(true, true, true);
+    else if (first) GA_SGD_LAUNCH(true, true, false);
+    else if (nesterov) GA_SGD_LAUNCH(true, false, true);
+    else GA_SGD_LAUNCH(true, false, false);
+#undef GA_SGD_LAUNCH
+    return check_launch("ga_sgd_step");
 }
 
 extern "C" GA_API int ga_probe_adam_placement(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,

@@ -27,6 +27,12 @@ where torch has no entry), and load_state_dict() (of an ArenaAdam or a
 torch.optim.Adam/AdamW state dict, with equal or different per-parameter
 steps) copies the loaded moments into those buffers, so a resumed run
 continues where it stopped.
+
+ArenaSGD is the same for OptimSpec(torch.optim.SGD, ...) (the "sgd" of
+OptimSpec.from_string, optim.py:24): one ga_sgd_step launch (read p, g, buf;
+write p, buf) with momentum, dampening, Nesterov and L2 weight decay, a
+per-parameter initialised flag where Adam has a step count.  build_fused picks
+the class for a spec; FUSED names both for the callers that step them.
 """
 import math
 import time
@@ -417,3 +423,220 @@ class ArenaAdam(torch.optim.Optimizer):
         return dict(lerp_w=1 - b1, beta2=b2, one_m_beta2=1 - b2, eps=eps,
                     wd_factor=(1 - lr * wd) if (decoupled and wd != 0) else 1.0,
                     l2_wd=wd if (not decoupled and wd != 0) else 0.0, step_size=-(lr / bc1), bc2_sqrt=math.sqrt(bc2))
+
+
+_SGD_KW = ("lr", "momentum", "dampening", "weight_decay", "nesterov")
+
+
+def fusable_sgd(spec_cls, kwargs, arena):
+    """True when OptimSpec(spec_cls, **kwargs) can run as ArenaSGD on this arena:
+    torch.optim.SGD on an fp32 arena with a gradient set, no maximize /
+    differentiable, a float learning rate."""
+    if spec_cls is not torch.optim.SGD:
+        return False
+    grads = getattr(arena, "grad_set", None) if hasattr(arena, "grad_set") else getattr(arena, "grad_flat", None)
+    if arena is None or grads is None or arena.dtype != torch.float32:
+        return False
+    kw = dict(kwargs or {})
+    if kw.get("maximize") or kw.get("differentiable"):
+        return False
+    if set(kw) - (set(_SGD_KW) | {"foreach", "fused", "maximize", "differentiable"}):
+        return False
+    return not isinstance(kw.get("lr", 1e-3), torch.Tensor)
+
+
+class ArenaSGD(torch.optim.Optimizer):
+    """torch.optim.SGD (momentum, dampening, Nesterov, L2 weight decay) over one
+    node's ParamArena or a ReplicaArena, built as ArenaAdam is: step() is one
+    ga_sgd_step launch over the [K, ld] sets (read p, g, buf; write p, buf) and,
+    with clipping, one ga_grad_clip_coef whose coefficient the step applies on
+    the device.
+
+    Exactness, as torch's: a parameter whose .grad is None at step time keeps its
+    value and its buffer; torch creates a parameter's momentum buffer as a clone
+    of the first gradient it ever sees (no dampening on that step), so every
+    parameter carries an *initialised* flag and a parameter that joins late takes
+    its own `first` launch while its neighbours take the ordinary one.  While
+    every parameter is present on one flag the step is one launch; otherwise the
+    kernel runs once per contiguous arena range of present parameters that share
+    the flag.  The buffer is one fp32 [K, ld] set (none while momentum is 0);
+    state[p]["momentum_buffer"] is a view of it once p has had a gradient and
+    None before (torch has no entry then), so state_dict() has torch's layout and
+    load_state_dict() takes an ArenaSGD or a torch.optim.SGD state dict."""
+
+    def __init__(self, params, arena, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False,
+                 placement=True, **ignored):
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                        maximize=False, foreach=None, differentiable=False, fused=None)
+        super().__init__(params, defaults)
+        if len(self.param_groups) != 1:
+            raise ValueError("ArenaSGD: one parameter group (the node's arena)")
+        self.arenas = list(getattr(arena, "arenas", [arena]))
+        self._arena = arena  # P and G are read from it at every use: the sets may be relocated
+        self.K, self.ld = self.P.shape
+        where = {}
+        for k, ar in enumerate(self.arenas):
+            for i, p in enumerate(ar.params):
+                where[id(p)] = (k, ar.layout.offsets[i], ar.layout.numels[i])
+        self._where = where
+        self._spans = [[] for _ in self.arenas]  # per replica: (param, offset, numel) in arena order
+        for p in self.param_groups[0]["params"]:
+            if id(p) not in where:
+                raise ValueError("ArenaSGD: every parameter must live in the arena")
+            k, o, n = where[id(p)]
+            self._spans[k].append((p, o, n))
+        for sp in self._spans:
+            sp.sort(key=lambda t: t[1])
+        self._B = None  # the momentum buffer [K, ld], allocated when momentum != 0
+        self._owner = None  # keeps a caller's buffer memory alive (move_buffer)
+        self._inited = set()  # ids of the parameters whose buffer holds their first gradient
+        if momentum != 0:
+            self._buffer()
+        dev = self.P.device
+        self._partials = ops.sumsq_partials(dev, self.K)
+        self._clip = torch.ones(2 * self.K, dtype=torch.float32, device=dev)
+        self.placement = {"placed": False, "why": "no search for SGD"}
+
+    P = ArenaAdam.P  # the parameter / gradient sets [K, ld], read from the arena at every use
+    G = ArenaAdam.G
+
+    @property
+    def B(self):
+        """The momentum buffer [K, ld] (None while momentum has been 0)."""
+        return self._B
+
+    def _buffer(self):
+        if self._B is None:
+            self._B = torch.zeros_like(self.P, dtype=torch.float32)
+            for p in self.param_groups[0]["params"]:
+                self._bind_state(p)
+        return self._B
+
+    def _bind_state(self, p):
+        k, o, n = self._where[id(p)]
+        self.state[p] = {"momentum_buffer": self._B[k, o:o + n].view(p.shape) if id(p) in self._inited else None}
+
+    def move_buffer(self, B, owner=None):
+        """Move the momentum buffer into another [K, ld] fp32 buffer (contents
+        copied, the per-parameter state re-pointed); `owner` keeps its memory
+        alive.  The counterpart of ArenaAdam.move_moments, for a caller that
+        wants the buffer in memory of its own."""
+        if B.shape != self.P.shape or B.dtype != torch.float32:
+            raise ValueError("ArenaSGD.move_buffer: a [K, ld] float32 buffer")
+        with torch.no_grad():
+            if self._B is not None:
+                B.copy_(self._B)
+            else:
+                B.zero_()
+        self._B, self._owner = B, owner
+        for p in self.param_groups[0]["params"]:
+            self._bind_state(p)
+
+    def load_state_dict(self, state_dict):
+        """torch's Optimizer.load_state_dict, then the loaded per-parameter
+        buffers are copied into the flat buffer the kernel reads and the state is
+        re-pointed at those views.  `momentum_buffer: None` or no entry: the
+        parameter is not initialised (its next gradient is its first)."""
+        super().load_state_dict(state_dict)
+        loaded = {id(p): self.state.get(p, {}).get("momentum_buffer") for p in self.param_groups[0]["params"]}
+        self._inited = {i for i, b in loaded.items() if b is not None}
+        if not self._inited and self._B is None and self.param_groups[0]["momentum"] == 0:
+            self.state.clear()
+            return
+        if self._B is None:
+            self._B = torch.zeros_like(self.P, dtype=torch.float32)
+        with torch.no_grad():
+            self._B.zero_()
+            for p in self.param_groups[0]["params"]:
+                if loaded[id(p)] is not None:
+                    k, o, n = self._where[id(p)]
+                    self._B[k, o:o + n].copy_(loaded[id(p)].reshape(-1))
+                self._bind_state(p)
+
+    @torch.no_grad()
+    def step(self, closure=None, max_norm=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        g = self.param_groups[0]
+        momentum = float(g["momentum"])
+        ranges, fresh = self._ranges(momentum != 0)
+        for ar in self.arenas:
+            ar.sync_grads()
+        if not any(ranges):  # no parameter has a gradient: torch's step does nothing
+            return loss
+        B = self._buffer() if momentum != 0 else None
+        clip = None
+        if max_norm:
+            ops.grad_clip_coef(self.G, self.ld, max_norm, self._partials, self._clip)
+            clip = self._clip
+        # neg_lr and 1 - dampening in double, rounded once (torch's alpha=-lr, alpha=1 - dampening)
+        hp = dict(neg_lr=-float(g["lr"]), momentum=momentum, one_m_dampening=1 - float(g["dampening"]),
+                  weight_decay=float(g["weight_decay"]), nesterov=bool(g["nesterov"]))
+        whole = ranges[0]
+        if whole and whole[0][:2] == (0, self.ld) and all(r == whole for r in ranges):
+            ops.sgd_step(self.P, self.G, B, first=whole[0][2], clip_coef=clip, **hp)
+        else:
+            for k in range(self.K):  # per replica: partial ranges, or flags apart
+                ck = clip[2 * k:2 * k + 2] if clip is not None else None
+                for a, b, first in ranges[k]:
+                    ops.sgd_step(self.P[k, a:b], self.G[k, a:b], B[k, a:b] if B is not None else None, first=first,
+                                 clip_coef=ck, **hp)
+        for p in fresh:  # their buffers now hold their first gradient
+            self._inited.add(id(p))
+            self._bind_state(p)
+        return loss
+
+    def _ranges(self, with_momentum):
+        """Per replica [(a, b, first)]: the contiguous ranges of present parameters
+        that share the flag (adjacent spans joined across the zero padding; the
+        whole row when all of a replica are present on one flag), and the list of
+        present parameters that are not initialised yet.  Without momentum there
+        is no buffer and no flag (torch creates none)."""
+        ranges, fresh = [], []
+        for k, spans in enumerate(self._spans):
+            out, present = [], 0
+            for p, o, n in spans:
+                if p.grad is None:
+                    continue
+                present += 1
+                first = with_momentum and id(p) not in self._inited
+                if first:
+                    fresh.append(p)
+                if out and o - out[-1][1] < 64 and out[-1][2] == first:  # adjacent (zero padding between), same flag
+                    out[-1][1] = o + n
+                else:
+                    out.append([o, o + n, first])
+            if len(out) == 1 and present == len(spans):
+                out = [[0, self.ld, out[0][2]]]
+            ranges.append([tuple(r) for r in out])
+        return ranges, fresh
+
+
+FUSED = (ArenaAdam, ArenaSGD)  # the inner optimizers whose step(max_norm=) clips on the device
+
+
+def build_fused(spec, params, arena, placement=True):
+    """The fused inner optimizer of OptimSpec `spec` over `arena` (ArenaAdam for
+    torch's AdamW / Adam, ArenaSGD for torch's SGD), or None when the spec stays
+    on torch: another optimizer or option, a bf16 arena, or GA_FUSED_OPTIM=0."""
+    import os
+    if os.environ.get("GA_FUSED_OPTIM", "1") == "0":
+        return None
+    kw = spec.kwargs or {}
+    if fusable(spec.cls, kw, arena):
+        kw = {k: v for k, v in kw.items() if k in ("lr", "betas", "eps", "weight_decay")}
+        return ArenaAdam(params, arena, decoupled=spec.cls is torch.optim.AdamW, placement=placement, **kw)
+    # a stand-in kernel layer (tests) written before ga_sgd_step keeps torch's SGD; gym_amd.ops always has it
+    if fusable_sgd(spec.cls, kw, arena) and hasattr(ops, "sgd_step"):
+        return ArenaSGD(params, arena, placement=placement, **{k: v for k, v in kw.items() if k in _SGD_KW})
+    return None

@@ -567,4 +567,27 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lerp_w, beta2, one_m_beta2, eps,
                              float(step_size), float(bc2_sqrt), _p(clip_coef), _stream()), "ga_adam_step")
 
 
+def sgd_step(param, grad, buf, *, neg_lr, momentum, one_m_dampening, weight_decay, nesterov, first, clip_coef=None,
+             n=None):
+    """One fused SGD step over fp32 [K, ld] replica sets (or 1-D buffers) of one
+    shape; every replica's first n elements (see include/gym_amd.h).  buf: the
+    momentum buffer, None only with momentum == 0."""
+    if buf is None and momentum != 0:
+        raise ValueError("sgd_step: a momentum buffer is required with momentum != 0")
+    ts = [_as2d(t) for t in (param, grad) + ((buf,) if buf is not None else ())]
+    _gpu(*ts, clip_coef)
+    K, ld = _rows_ld(ts[0])
+    for t in ts:
+        if t.dtype != torch.float32 or t.shape != ts[0].shape or t.stride() != ts[0].stride() or t.stride(-1) != 1:
+            raise ValueError("sgd_step: param/grad/buf must be fp32 replica sets of one layout")
+    n = ts[0].shape[1] if n is None else int(n)
+    if n < 0 or n > ts[0].shape[1]:
+        raise ValueError("sgd_step: n exceeds the row length (ld < n)")
+    if clip_coef is not None and clip_coef.numel() < 2 * K:
+        raise ValueError("sgd_step: clip_coef must hold 2 floats per replica")
+    check(lib().ga_sgd_step(_GA_F32, _p(ts[0]), _p(ts[1]), _p(ts[2]) if buf is not None else None, K, ld, n,
+                            float(neg_lr), float(momentum), float(one_m_dampening), float(weight_decay),
+                            int(bool(nesterov)), int(bool(first)), _p(clip_coef), _stream()), "ga_sgd_step")
+
+
 _GA_F32 = _lib.GA_F32

@@ -42,7 +42,7 @@ from . import ops
 from .arena import ReplicaArena
 from .comm import Collective
 from .engine import DiLoCoOuter, MeanReduce, Sparta, demo_codec
-from .fused_optim import ArenaAdam, fusable
+from .fused_optim import FUSED, build_fused
 from .strategy.demo import DeMoStrategy
 from .strategy.diloco import DiLoCoStrategy, fused_sgd_hparams
 from .strategy.federated_averaging import FedAvgStrategy
@@ -144,12 +144,9 @@ class ReplicaRunner:
             self.placement, self._placed = None, None
         else:
             spec = s.optim_spec if isinstance(s, SimpleReduceStrategy) else s.inner_optim_spec
-            if fusable(spec.cls, spec.kwargs, self.ra):
-                kw = {k: v for k, v in (spec.kwargs or {}).items() if k in ("lr", "betas", "eps", "weight_decay")}
-                self.optim = ArenaAdam(self.ra.params, self.ra, decoupled=spec.cls is torch.optim.AdamW,
-                                       placement=s.placement_opt, **kw)
-            else:
-                self.optim = _PerNodeOptim(spec, models, self.ra.arenas)
+            # one fused launch over all K nodes (ArenaAdam / ArenaSGD), or K torch optimizers
+            self.optim = (build_fused(spec, self.ra.params, self.ra, s.placement_opt)
+                          or _PerNodeOptim(spec, models, self.ra.arenas))
             self.max_norm = s.kwargs.get("max_norm") if isinstance(s, DiLoCoStrategy) else s.max_norm
             if isinstance(s, (DiLoCoStrategy, SPARTADiLoCoStrategy)):
                 hp = fused_sgd_hparams(s.outer_optim_spec)
@@ -381,7 +378,7 @@ class ReplicaRunner:
         return self.bits
 
     def _inner(self):
-        if isinstance(self.optim, ArenaAdam):
+        if isinstance(self.optim, FUSED):
             self.optim.step(max_norm=self.max_norm or None)
         else:
             self.optim.step(max_norm=self.max_norm)

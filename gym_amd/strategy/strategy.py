@@ -10,7 +10,8 @@ zero_grad(), __config__()).  What changes underneath:
   (strategy.py:130-133) becomes ONE RCCL all-reduce over the gradient arena
   plus ONE division kernel (ga_replica_mean);
 - gradient clipping + the default AdamW step run over the arena as one norm
-  reduction and one fused kernel (gym_amd.fused_optim.ArenaAdam);
+  reduction and one fused kernel (gym_amd.fused_optim.ArenaAdam; ArenaSGD for
+  an SGD spec);
 - zero_grad() zeroes the gradient arena in place (grads stay bound to it)
   instead of setting them to None.
 """
@@ -37,23 +38,20 @@ def require_gpu(device):
 
 
 def build_inner_optimizer(spec, model, arena, placement=True):
-    """The node's inner optimizer: torch's AdamW/Adam become ArenaAdam (one fused
-    kernel over the arena per step, gym_amd.fused_optim); any other OptimSpec is
-    built as in the reference (OptimSpec.build, optim.py:38-39).  GA_FUSED_OPTIM=0
-    keeps torch's optimizer."""
-    import os
-    from ..fused_optim import ArenaAdam, fusable
-    if os.environ.get("GA_FUSED_OPTIM", "1") != "0" and fusable(spec.cls, spec.kwargs, arena):
-        kw = {k: v for k, v in (spec.kwargs or {}).items() if k in ("lr", "betas", "eps", "weight_decay")}
-        return ArenaAdam(model.parameters(), arena, decoupled=spec.cls is torch.optim.AdamW, placement=placement, **kw)
-    return spec.build(model)
+    """The node's inner optimizer: torch's AdamW/Adam become ArenaAdam and torch's
+    SGD becomes ArenaSGD (one fused kernel over the arena per step,
+    gym_amd.fused_optim.build_fused); any other OptimSpec is built as in the
+    reference (OptimSpec.build, optim.py:38-39).  GA_FUSED_OPTIM=0 keeps torch's
+    optimizer."""
+    from ..fused_optim import build_fused
+    return build_fused(spec, model.parameters(), arena, placement) or spec.build(model)
 
 
 def clip_and_step(strategy, max_norm):
     """clip_grad_norm_(max_norm) (if set) then the inner optimizer step; fused
-    into the ArenaAdam step (norm reduction + device-side coefficient)."""
-    from ..fused_optim import ArenaAdam
-    if isinstance(strategy.optim, ArenaAdam):
+    into the ArenaAdam / ArenaSGD step (norm reduction + device-side coefficient)."""
+    from ..fused_optim import FUSED
+    if isinstance(strategy.optim, FUSED):
         strategy.optim.step(max_norm=max_norm or None)
         return
     if max_norm:

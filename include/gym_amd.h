@@ -509,6 +509,32 @@ GA_API int ga_adam_step(int dtype, void* param, void* grad, float* exp_avg, floa
                         float wd_factor, float l2_wd, float step_size, float bc2_sqrt, const float* clip_coef,
                         hipStream_t stream);
 
+/*
+ * One fused SGD step (momentum, dampening, Nesterov, L2 weight decay) over K
+ * replicas of an fp32 arena (param, grad, momentum_buf: [K, ld] sets, n elements
+ * per replica, 16-byte aligned), every replica with the same hyper-parameters, in
+ * torch's op order (torch/optim/sgd.py, _single_tensor_sgd / _multi_tensor_sgd):
+ *   g = grad * clip_coef[2k]  (and written back) if clip_coef != null and !(clip_coef[2k] >= 1):
+ *                             a NaN coefficient scales too (ga_adam_step's rule)
+ *   g += weight_decay * p     (weight_decay != 0; not written back)
+ *   momentum != 0:
+ *     buf = g                                    if first (torch clones the first gradient: no dampening)
+ *         | momentum*buf + one_m_dampening*g     otherwise
+ *     g   = g + momentum*buf (nesterov) | buf
+ *   p += neg_lr * g
+ * neg_lr = -lr and one_m_dampening = 1 - dampening are computed by the caller in
+ * double.  With momentum == 0 momentum_buf may be null and is neither read nor
+ * written; with `first` set it is written and not read.  Bytes per element: 12
+ * without momentum, 20 with, 16 on a first step, +4 when the clipped gradient is
+ * written back.
+ * Replaces: `self.optim.step()` with OptimSpec(torch.optim.SGD, ...), the "sgd" of
+ * OptimSpec.from_string (exogym/strategy/optim.py:24; strategy.py:135-140,
+ * diloco.py:52-59, communicate_optimize_strategy.py:69-74).
+ */
+GA_API int ga_sgd_step(int dtype, void* param, void* grad, float* momentum_buf, int64_t K, int64_t ld, int64_t n,
+                       float neg_lr, float momentum, float one_m_dampening, float weight_decay, int nesterov,
+                       int first, const float* clip_coef, hipStream_t stream);
+
 /* ---- node drift: model correlation and consensus distance ---------------- */
 
 /* Bytes of the `work` buffer ga_replica_gram needs for K replicas of n elements
