@@ -28,129 +28,104 @@ constexpr int kOptBlock = 256;
 constexpr int64_t kOptChunk = 1024;  // float4 vectors per workgroup
 constexpr int kSumsqBlocks = 1024;   // partials of the norm reduction
 
-__global__ __launch_bounds__(kOptBlock) void adam_kernel(float* __restrict__ param, float* __restrict__ grad,
-                                                         float* __restrict__ m_, float* __restrict__ v_, int64_t n,
-                                                         int64_t ld, AdamParams ap,
-                                                         const float* __restrict__ clip_coef) {
-    const int64_t rep = blockIdx.y;  // replica (simulated node) of a [K, ld] set
+// What one pass does per element.  An operation states at compile time its fp32 state
+// streams (kStates), whether they are loaded (kLoad; they are always stored), whether
+// the clip coefficient applies (kClip) and whether the n % 4 tail exists (kTail), and
+// updates one element: operator()(p, g, s), s the element's kStates state values.
+struct AdamOp {  // ga_adam_step: exp_avg, exp_avg_sq
+    static constexpr int kStates = 2;
+    static constexpr bool kLoad = true, kClip = true, kTail = true;
+    AdamParams ap;
+    __device__ __forceinline__ void operator()(float& p, float& g, float* s) const { adam_elem(p, g, s[0], s[1], ap); }
+};
+
+// ga_sgd_step.  kMomentum / kFirst / kNesterov are uniform over a launch; without
+// momentum there is no state stream and the buffer pointer is never touched (it may be
+// null), on a first step the buffer is written and not read.
+template <bool kMomentum, bool kFirst, bool kNesterov>
+struct SgdOp {
+    static constexpr int kStates = kMomentum ? 1 : 0;
+    static constexpr bool kLoad = !kFirst, kClip = true, kTail = true;
+    SgdParams sp;
+    __device__ __forceinline__ void operator()(float& p, float& g, float* s) const {
+        sgd_elem<kMomentum, kFirst, kNesterov>(p, g, s[0], sp);
+    }
+};
+
+// Placement probe of AdamOp (no reference counterpart): its exact access pattern (p, g,
+// m, v read, p, m, v written through the same stores) with every value written back
+// unchanged, so ArenaAdam can time candidate physical buffers for the moments without
+// side effects.  No clip and no tail: ga_probe_adam_placement requires n % 4 == 0.
+struct AdamProbeOp {
+    static constexpr int kStates = 2;
+    static constexpr bool kLoad = true, kClip = false, kTail = false;
+    __device__ __forceinline__ void operator()(float&, float& g, float*) const {
+        asm volatile("" ::"v"(g));  // the grad load stays live
+    }
+};
+
+// The one streaming pass of the inner optimizers over [K, ld] sets: the replica
+// (simulated node) on grid.y, kOptChunk float4 per workgroup, nt loads, the clipped
+// gradient written back (clip_grad_norm_ leaves the clipped grads), sc1 stores, the
+// scalar tail (n % 4) in the last workgroup.  s0 / s1 are the operation's state streams.
+template <typename Op>
+__global__ __launch_bounds__(kOptBlock) void opt_pass(float* __restrict__ param, float* __restrict__ grad,
+                                                       float* __restrict__ s0, float* __restrict__ s1, int64_t n,
+                                                       int64_t ld, Op op, const float* __restrict__ clip_coef) {
+    constexpr int kS = Op::kStates, kSN = kS > 0 ? kS : 1;
+    const int64_t rep = blockIdx.y;
     param += rep * ld;
     grad += rep * ld;
-    m_ += rep * ld;
-    v_ += rep * ld;
-    const float coef = clip_coef ? clip_coef[2 * rep] : 1.f;
+    float* st[2] = {s0, s1};
+#pragma unroll
+    for (int k = 0; k < kS; ++k) st[k] += rep * ld;
+    float coef = 1.f;
+    if constexpr (Op::kClip) coef = clip_coef ? clip_coef[2 * rep] : 1.f;
     const bool scale = !(coef >= 1.f);  // a NaN coefficient scales too (clamp(nan, max=1) is nan)
     const int64_t nv = n >> 2;
     const int64_t lo = (int64_t)blockIdx.x * kOptChunk;
     const int64_t hi = lo + kOptChunk < nv ? lo + kOptChunk : nv;
     for (int64_t i = lo + threadIdx.x; i < hi; i += kOptBlock) {
-        float4 p = stream_load(reinterpret_cast<const float4*>(param) + i);
-        float4 g = stream_load(reinterpret_cast<const float4*>(grad) + i);
-        float4 m = stream_load(reinterpret_cast<const float4*>(m_) + i);
-        float4 v = stream_load(reinterpret_cast<const float4*>(v_) + i);
-        if (scale) {
-            g.x *= coef; g.y *= coef; g.z *= coef; g.w *= coef;
-            stream_store(reinterpret_cast<float4*>(grad) + i, g);  // clip_grad_norm_ leaves the clipped grads
-        }
-        float gg[4] = {g.x, g.y, g.z, g.w};
-        float pp[4] = {p.x, p.y, p.z, p.w}, mm[4] = {m.x, m.y, m.z, m.w}, vv[4] = {v.x, v.y, v.z, v.w};
+        float pp[4], gg[4], ss[kSN][4] = {};
+        Vec4<float>::unpack(stream_load(reinterpret_cast<const float4*>(param) + i), pp);
+        Vec4<float>::unpack(stream_load(reinterpret_cast<const float4*>(grad) + i), gg);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) adam_elem(pp[e], gg[e], mm[e], vv[e], ap);
-        const uint32_t o = (uint32_t)(i - lo);
-        store_sc1(reinterpret_cast<float4*>(param) + lo, o, make_float4(pp[0], pp[1], pp[2], pp[3]));
-        store_sc1(reinterpret_cast<float4*>(m_) + lo, o, make_float4(mm[0], mm[1], mm[2], mm[3]));
-        store_sc1(reinterpret_cast<float4*>(v_) + lo, o, make_float4(vv[0], vv[1], vv[2], vv[3]));
-    }
-    // scalar tail (n % 4), handled by the last workgroup
-    if (blockIdx.x == gridDim.x - 1) {
-        for (int64_t j = (nv << 2) + threadIdx.x; j < n; j += kOptBlock) {
-            float p = param[j], g = grad[j], m = m_[j], v = v_[j];
-            if (scale) {
-                g *= coef;
-                grad[j] = g;
-            }
-            adam_elem(p, g, m, v, ap);
-            param[j] = p;
-            m_[j] = m;
-            v_[j] = v;
-        }
-    }
-}
-
-// SGD over the arena, adam_kernel's shape: replicas on grid.y, kOptChunk float4 per
-// workgroup, nt loads, sc1 stores.  kMomentum / kFirst / kNesterov are uniform over a
-// launch; without momentum the buffer pointer is never touched (it may be null), on a
-// first step it is written and not read.
-template <bool kMomentum, bool kFirst, bool kNesterov>
-__global__ __launch_bounds__(kOptBlock) void sgd_kernel(float* __restrict__ param, float* __restrict__ grad,
-                                                        float* __restrict__ buf_, int64_t n, int64_t ld,
-                                                        SgdParams sp, const float* __restrict__ clip_coef) {
-    const int64_t rep = blockIdx.y;
-    param += rep * ld;
-    grad += rep * ld;
-    if (kMomentum) buf_ += rep * ld;
-    const float coef = clip_coef ? clip_coef[2 * rep] : 1.f;
-    const bool scale = !(coef >= 1.f);  // a NaN coefficient scales too (ga_adam_step's rule)
-    const int64_t nv = n >> 2;
-    const int64_t lo = (int64_t)blockIdx.x * kOptChunk;
-    const int64_t hi = lo + kOptChunk < nv ? lo + kOptChunk : nv;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += kOptBlock) {
-        float4 p = stream_load(reinterpret_cast<const float4*>(param) + i);
-        float4 g = stream_load(reinterpret_cast<const float4*>(grad) + i);
-        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (kMomentum && !kFirst) b = stream_load(reinterpret_cast<const float4*>(buf_) + i);
+        for (int k = 0; k < kS; ++k)
+            if (Op::kLoad) Vec4<float>::unpack(stream_load(reinterpret_cast<const float4*>(st[k]) + i), ss[k]);
         if (scale) {
-            g.x *= coef; g.y *= coef; g.z *= coef; g.w *= coef;
-            stream_store(reinterpret_cast<float4*>(grad) + i, g);  // clip_grad_norm_ leaves the clipped grads
-        }
-        float pp[4] = {p.x, p.y, p.z, p.w}, gg[4] = {g.x, g.y, g.z, g.w}, bb[4] = {b.x, b.y, b.z, b.w};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) sgd_elem<kMomentum, kFirst, kNesterov>(pp[e], gg[e], bb[e], sp);
-        const uint32_t o = (uint32_t)(i - lo);
-        store_sc1(reinterpret_cast<float4*>(param) + lo, o, make_float4(pp[0], pp[1], pp[2], pp[3]));
-        if (kMomentum) store_sc1(reinterpret_cast<float4*>(buf_) + lo, o, make_float4(bb[0], bb[1], bb[2], bb[3]));
-    }
-    // scalar tail (n % 4), handled by the last workgroup
-    if (blockIdx.x == gridDim.x - 1) {
-        for (int64_t j = (nv << 2) + threadIdx.x; j < n; j += kOptBlock) {
-            float p = param[j], g = grad[j], b = 0.f;
-            if (kMomentum && !kFirst) b = buf_[j];
-            if (scale) {
-                g *= coef;
-                grad[j] = g;
-            }
-            sgd_elem<kMomentum, kFirst, kNesterov>(p, g, b, sp);
-            param[j] = p;
-            if (kMomentum) buf_[j] = b;
+            for (int e = 0; e < 4; ++e) gg[e] *= coef;
+            stream_store(reinterpret_cast<float4*>(grad) + i, Vec4<float>::pack(gg));
         }
-    }
-}
-
-// Placement probe of adam_kernel (no reference counterpart): its exact access pattern
-// (replicas on grid.y, 1024 float4 per workgroup, p, g, m, v read, p, m, v written
-// through the same stores) with every value written back unchanged, so ArenaAdam can
-// time candidate physical buffers for the moments without side effects.
-__global__ __launch_bounds__(kOptBlock) void adam_probe_kernel(float* __restrict__ param,
-                                                               const float* __restrict__ grad,
-                                                               float* __restrict__ m_, float* __restrict__ v_,
-                                                               int64_t n, int64_t ld) {
-    const int64_t rep = blockIdx.y;
-    param += rep * ld;
-    grad += rep * ld;
-    m_ += rep * ld;
-    v_ += rep * ld;
-    const int64_t nv = n >> 2;
-    const int64_t lo = (int64_t)blockIdx.x * kOptChunk;
-    const int64_t hi = lo + kOptChunk < nv ? lo + kOptChunk : nv;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += kOptBlock) {
-        const float4 p = stream_load(reinterpret_cast<const float4*>(param) + i);
-        const float4 g = stream_load(reinterpret_cast<const float4*>(grad) + i);
-        const float4 m = stream_load(reinterpret_cast<const float4*>(m_) + i);
-        const float4 v = stream_load(reinterpret_cast<const float4*>(v_) + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float s[kSN];
+            for (int k = 0; k < kSN; ++k) s[k] = ss[k][e];
+            op(pp[e], gg[e], s);
+            for (int k = 0; k < kSN; ++k) ss[k][e] = s[k];
+        }
         const uint32_t o = (uint32_t)(i - lo);
-        asm volatile("" ::"v"(g.x), "v"(g.y), "v"(g.z), "v"(g.w));  // the grad load stays live
-        store_sc1(reinterpret_cast<float4*>(param) + lo, o, p);
-        store_sc1(reinterpret_cast<float4*>(m_) + lo, o, m);
-        store_sc1(reinterpret_cast<float4*>(v_) + lo, o, v);
+        store_sc1(reinterpret_cast<float4*>(param) + lo, o, Vec4<float>::pack(pp));
+#pragma unroll
+        for (int k = 0; k < kS; ++k) store_sc1(reinterpret_cast<float4*>(st[k]) + lo, o, Vec4<float>::pack(ss[k]));
+    }
+    if constexpr (Op::kTail) {
+        if (blockIdx.x == gridDim.x - 1) {
+            for (int64_t j = (nv << 2) + threadIdx.x; j < n; j += kOptBlock) {
+                float p = param[j], g = grad[j], s[kSN] = {};
+#pragma unroll
+                for (int k = 0; k < kS; ++k)
+                    if (Op::kLoad) s[k] = st[k][j];
+                if (scale) {
+                    g *= coef;
+                    grad[j] = g;
+                }
+                op(p, g, s);
+                param[j] = p;
+#pragma unroll
+                for (int k = 0; k < kS; ++k) st[k][j] = s[k];
+            }
+        }
     }
 }
 
@@ -236,70 +211,79 @@ extern "C" GA_API int ga_grad_clip_coef(int dtype, const void* grad, int64_t K, 
     return check_launch("ga_grad_clip_coef");
 }
 
+// What every pass requires of its sizes, in the entry point's name; *grid = workgroups
+// per replica, 0 when there is nothing to do (n == 0).
+static int opt_grid(const char* who, bool sizes_ok, int64_t n, int64_t K, int64_t ld, int64_t* grid) {
+    *grid = 0;
+    GA_REQUIRE(sizes_ok && n >= 0 && K >= 1 && K <= 65535, "%s: bad sizes n=%lld K=%lld", who, (long long)n,
+               (long long)K);
+    if (n == 0) return GA_OK;
+    GA_REQUIRE(K == 1 || (ld >= n && ld % 4 == 0), "%s: ld must be >= n and a multiple of 4", who);
+    const int64_t g = (n / 4 + kOptChunk - 1) / kOptChunk;
+    *grid = g < 1 ? 1 : g;
+    return GA_OK;
+}
+
+static bool aligned16(const void* a, const void* b, const void* c = nullptr, const void* d = nullptr) {
+    return ((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) % 16 == 0;
+}
+
+template <typename Op>
+static int opt_launch(const char* who, int64_t grid, int64_t K, hipStream_t stream, float* param, float* grad,
+                      float* s0, float* s1, int64_t n, int64_t ld, Op op, const float* clip_coef) {
+    hipLaunchKernelGGL(opt_pass<Op>, dim3((unsigned)grid, (unsigned)K), dim3(kOptBlock), 0, stream, param, grad, s0,
+                       s1, n, ld, op, clip_coef);
+    return check_launch(who);
+}
+
 extern "C" GA_API int ga_adam_step(int dtype, void* param, void* grad, float* exp_avg, float* exp_avg_sq, int64_t K,
                                    int64_t ld, int64_t n, float lerp_w, float beta2, float one_m_beta2, float eps,
                                    float wd_factor, float l2_wd, float step_size, float bc2_sqrt,
                                    const float* clip_coef, hipStream_t stream) {
     clear_error();
-    GA_REQUIRE(n >= 0 && K >= 1 && K <= 65535, "ga_adam_step: bad sizes n=%lld K=%lld", (long long)n, (long long)K);
-    if (n == 0) return GA_OK;
-    GA_REQUIRE(K == 1 || (ld >= n && ld % 4 == 0), "ga_adam_step: ld must be >= n and a multiple of 4");
+    int64_t grid;
+    if (int e = opt_grid("ga_adam_step", true, n, K, ld, &grid)) return e;
+    if (grid == 0) return GA_OK;
     GA_REQUIRE(param && grad && exp_avg && exp_avg_sq, "ga_adam_step: null buffer");
     GA_REQUIRE(dtype == GA_F32, "ga_adam_step: only float32 arenas are fused (dtype %d)", dtype);
-    GA_REQUIRE(((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0,
-               "ga_adam_step: buffers must be 16-byte aligned");
+    GA_REQUIRE(aligned16(param, grad, exp_avg, exp_avg_sq), "ga_adam_step: buffers must be 16-byte aligned");
     GA_REQUIRE(bc2_sqrt > 0.f, "ga_adam_step: bc2_sqrt must be > 0");
-    const AdamParams ap{lerp_w, beta2, one_m_beta2, eps, wd_factor, l2_wd, step_size, bc2_sqrt};
-    const int64_t nv = n / 4;
-    int64_t grid = (nv + kOptChunk - 1) / kOptChunk;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)grid, (unsigned)K), dim3(kOptBlock), 0, stream, (float*)param,
-                       (float*)grad, exp_avg, exp_avg_sq, n, ld, ap, clip_coef);
-    return check_launch("ga_adam_step");
+    const AdamOp op{{lerp_w, beta2, one_m_beta2, eps, wd_factor, l2_wd, step_size, bc2_sqrt}};
+    return opt_launch("ga_adam_step", grid, K, stream, (float*)param, (float*)grad, exp_avg, exp_avg_sq, n, ld, op,
+                      clip_coef);
 }
 
 extern "C" GA_API int ga_sgd_step(int dtype, void* param, void* grad, float* momentum_buf, int64_t K, int64_t ld,
                                   int64_t n, float neg_lr, float momentum, float one_m_dampening, float weight_decay,
                                   int nesterov, int first, const float* clip_coef, hipStream_t stream) {
     clear_error();
-    GA_REQUIRE(n >= 0 && K >= 1 && K <= 65535, "ga_sgd_step: bad sizes n=%lld K=%lld", (long long)n, (long long)K);
-    if (n == 0) return GA_OK;
-    GA_REQUIRE(K == 1 || (ld >= n && ld % 4 == 0), "ga_sgd_step: ld must be >= n and a multiple of 4");
+    int64_t grid;
+    if (int e = opt_grid("ga_sgd_step", true, n, K, ld, &grid)) return e;
+    if (grid == 0) return GA_OK;
     const bool mom = momentum != 0.f;
     GA_REQUIRE(param && grad, "ga_sgd_step: null buffer");
     GA_REQUIRE(!mom || momentum_buf, "ga_sgd_step: null momentum buffer with momentum %g", (double)momentum);
     GA_REQUIRE(dtype == GA_F32, "ga_sgd_step: only float32 arenas are fused (dtype %d)", dtype);
-    GA_REQUIRE(((uintptr_t)param | (uintptr_t)grad | (mom ? (uintptr_t)momentum_buf : 0)) % 16 == 0,
-               "ga_sgd_step: buffers must be 16-byte aligned");
+    GA_REQUIRE(aligned16(param, grad, mom ? momentum_buf : nullptr), "ga_sgd_step: buffers must be 16-byte aligned");
     const SgdParams sp{neg_lr, momentum, one_m_dampening, weight_decay};
-    int64_t g = (n / 4 + kOptChunk - 1) / kOptChunk;
-    if (g < 1) g = 1;
-    const dim3 grid((unsigned)g, (unsigned)K), block(kOptBlock);
-    float *p = (float*)param, *gr = (float*)grad;
-#define GA_SGD_LAUNCH(M, F, N) \
-    hipLaunchKernelGGL((sgd_kernel<M, F, N>), grid, block, 0, stream, p, gr, momentum_buf, n, ld, sp, clip_coef)
-    if (!mom) GA_SGD_LAUNCH(false, false, false);
-    else if (first && nesterov) GA_SGD_LAUNCH(true, true, true);
-    else if (first) GA_SGD_LAUNCH(true, true, false);
-    else if (nesterov) GA_SGD_LAUNCH(true, false, true);
-    else GA_SGD_LAUNCH(true, false, false);
+#define GA_SGD_LAUNCH(M, F, N)                                                                                  \
+    opt_launch("ga_sgd_step", grid, K, stream, (float*)param, (float*)grad, momentum_buf, nullptr, n, ld, \
+               SgdOp<M, F, N>{sp}, clip_coef)
+    if (!mom) return GA_SGD_LAUNCH(false, false, false);
+    if (first) return nesterov ? GA_SGD_LAUNCH(true, true, true) : GA_SGD_LAUNCH(true, true, false);
+    return nesterov ? GA_SGD_LAUNCH(true, false, true) : GA_SGD_LAUNCH(true, false, false);
 #undef GA_SGD_LAUNCH
-    return check_launch("ga_sgd_step");
 }
 
 extern "C" GA_API int ga_probe_adam_placement(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                                               int64_t K, int64_t ld, int64_t n, hipStream_t stream) {
     clear_error();
-    GA_REQUIRE(n >= 0 && n % 4 == 0 && K >= 1 && K <= 65535, "ga_probe_adam_placement: bad sizes n=%lld K=%lld",
-               (long long)n, (long long)K);
-    if (n == 0) return GA_OK;
-    GA_REQUIRE(K == 1 || (ld >= n && ld % 4 == 0), "ga_probe_adam_placement: ld must be >= n and a multiple of 4");
+    int64_t grid;
+    if (int e = opt_grid("ga_probe_adam_placement", n % 4 == 0, n, K, ld, &grid)) return e;
+    if (grid == 0) return GA_OK;
     GA_REQUIRE(param && grad && exp_avg && exp_avg_sq, "ga_probe_adam_placement: null buffer");
-    GA_REQUIRE(((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0,
-               "ga_probe_adam_placement: buffers must be 16-byte aligned");
-    int64_t grid = (n / 4 + kOptChunk - 1) / kOptChunk;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(adam_probe_kernel, dim3((unsigned)grid, (unsigned)K), dim3(kOptBlock), 0, stream, param, grad,
-                       exp_avg, exp_avg_sq, n, ld);
-    return check_launch("ga_probe_adam_placement");
+    GA_REQUIRE(aligned16(param, grad, exp_avg, exp_avg_sq), "ga_probe_adam_placement: buffers must be 16-byte aligned");
+    // the probe never writes the gradient (no clip)
+    return opt_launch("ga_probe_adam_placement", grid, K, stream, param, const_cast<float*>(grad), exp_avg,
+                      exp_avg_sq, n, ld, AdamProbeOp{}, nullptr);
 }

@@ -96,10 +96,52 @@ __device__ __forceinline__ float outer_update(float sum, float& master, float& b
     return master;
 }
 
-template <typename T, typename M, bool VEC>
+// The value an arena of dtype T holds after storing x (SPARTA writes its average
+// to the replicas before the outer step reads them back).
+template <typename T> __device__ __forceinline__ float round_to(float x);
+template <> __device__ __forceinline__ float round_to<float>(float x) { return x; }
+template <> __device__ __forceinline__ float round_to<__hip_bfloat16>(float x) {
+    return __bfloat162float(__float2bfloat16(x));
+}
+
+// What the outer step sums over an element SPARTA averaged just before it: every
+// replica then holds a = sum / sparse_divisor rounded to T, and the ascending
+// fp32 sum of K copies of a is K additions (not K * a: the partial sums round).
+template <typename T>
+__device__ __forceinline__ float sum_of_sparse_average(float sum, float sparse_divisor, int64_t K) {
+    const float a = round_to<T>(sum / sparse_divisor);
+    float s = 0.f;
+    for (int64_t k = 0; k < K; ++k) s += a;
+    return s;
+}
+
+// Which elements of the outer step take sum_of_sparse_average instead of the plain
+// replica sum.  DenseSel (ga_diloco_outer): none, and the kernel holds no mask code.
+// SparseSel (ga_diloco_outer_masked, SPARTA's sparse average followed by the outer
+// step in the outer step's one pass): those whose bit is set in `bits` (bit j of word
+// w = element 64 w + j).  A lane's 4 elements are one nibble of a word, the 16 lanes
+// of a word load the same 8 bytes; at SPARTA's rates the nibble is almost always 0
+// and the selected branch is skipped.
+struct DenseSel {};
+struct SparseSel {
+    const uint64_t* __restrict__ bits;
+    float sparse_divisor;
+    __device__ __forceinline__ uint32_t nibble(int64_t v) const {
+        return (uint32_t)(bits[v >> 4] >> ((v & 15) * 4)) & 0xfu;
+    }
+    __device__ __forceinline__ bool bit(int64_t i) const { return bits[i >> 6] >> (i & 63) & 1ull; }
+};
+
+template <typename T, typename M, bool VEC, typename Sel>
 __global__ __launch_bounds__(kBlock) void diloco_outer_kernel(
     const T* src, int64_t K, int64_t ld_src, int64_t n, M* master, M* mom,
-    OuterParams op, T* dst, int64_t K_out, int64_t ld_dst) {
+    OuterParams op, T* dst, int64_t K_out, int64_t ld_dst, Sel sel) {
+    constexpr bool kSparse = !std::is_same<Sel, DenseSel>::value;
+    if constexpr (kSparse) {  // in place over all K rows, as ga_diloco_outer_masked requires: one K, one ld
+        dst = const_cast<T*>(src);
+        K_out = K;
+        ld_dst = ld_src;
+    }
     const bool has_mom = op.momentum != 0.f;
     int64_t lo, hi;
     if constexpr (VEC) {
@@ -107,6 +149,8 @@ __global__ __launch_bounds__(kBlock) void diloco_outer_kernel(
         using VM = typename Vec4<M>::type;
         chunk_range(n >> 2, lo, hi);
         for (int64_t v = lo + threadIdx.x; v < hi; v += kBlock) {
+            uint32_t nib = 0;
+            if constexpr (kSparse) nib = sel.nibble(v);
             float acc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 8
             for (int64_t k = 0; k < K; ++k) {
@@ -114,6 +158,13 @@ __global__ __launch_bounds__(kBlock) void diloco_outer_kernel(
                 Vec4<T>::unpack(stream_load(reinterpret_cast<const V*>(src + k * ld_src) + v), f);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc[e] += f[e];
+            }
+            if constexpr (kSparse) {
+                if (nib) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (nib >> e & 1u) acc[e] = sum_of_sparse_average<T>(acc[e], sel.sparse_divisor, K);
+                }
             }
             float m[4], b[4] = {0.f, 0.f, 0.f, 0.f};
             Vec4<M>::unpack(stream_load(reinterpret_cast<const VM*>(master) + v), m);
@@ -134,6 +185,9 @@ __global__ __launch_bounds__(kBlock) void diloco_outer_kernel(
             float acc = 0.f;
 #pragma unroll 4
             for (int64_t k = 0; k < K; ++k) acc += Elem<T>::load(src + k * ld_src + i);
+            if constexpr (kSparse) {
+                if (sel.bit(i)) acc = sum_of_sparse_average<T>(acc, sel.sparse_divisor, K);
+            }
             float m = Elem<M>::load(master + i);
             float b = (has_mom && !op.first_step) ? Elem<M>::load(mom + i) : 0.f;
             const float out = outer_update(acc, m, b, op);
@@ -144,87 +198,8 @@ __global__ __launch_bounds__(kBlock) void diloco_outer_kernel(
     }
 }
 
-// The value an arena of dtype T holds after storing x (SPARTA writes its average
-// to the replicas before the outer step reads them back).
-template <typename T> __device__ __forceinline__ float round_to(float x);
-template <> __device__ __forceinline__ float round_to<float>(float x) { return x; }
-template <> __device__ __forceinline__ float round_to<__hip_bfloat16>(float x) {
-    return __bfloat162float(__float2bfloat16(x));
-}
-
-// What the outer step sums over an element SPARTA averaged just before it: every
-// replica then holds a = sum / sparse_divisor rounded to T, and the ascending
-// fp32 sum of K copies of a is K additions (not K * a: the partial sums round).
-template <typename T>
-__device__ __forceinline__ float sum_of_sparse_average(float sum, float sparse_divisor, int64_t K) {
-    const float a = round_to<T>(sum / sparse_divisor);
-    float s = 0.f;
-    for (int64_t k = 0; k < K; ++k) s += a;
-    return s;
-}
-
-// SPARTA's sparse average followed by the outer step, in the outer step's one pass
-// (ga_diloco_outer_masked): diloco_outer_kernel in place over all K rows, with the
-// elements whose bit is set in `bits` (bit j of word w = element 64 w + j) taking
-// sum_of_sparse_average.  A lane's 4 elements are one nibble of a word, the 16
-// lanes of a word load the same 8 bytes; at SPARTA's rates the nibble is almost
-// always 0 and the selected branch is skipped.
-template <typename T, typename M, bool VEC>
-__global__ __launch_bounds__(kBlock) void diloco_outer_masked_kernel(
-    T* src, int64_t K, int64_t ld, int64_t n, const uint64_t* __restrict__ bits, float sparse_divisor,
-    M* master, M* mom, OuterParams op) {
-    const bool has_mom = op.momentum != 0.f;
-    int64_t lo, hi;
-    if constexpr (VEC) {
-        using V = typename Vec4<T>::type;
-        using VM = typename Vec4<M>::type;
-        chunk_range(n >> 2, lo, hi);
-        for (int64_t v = lo + threadIdx.x; v < hi; v += kBlock) {
-            const uint32_t nib = (uint32_t)(bits[v >> 4] >> ((v & 15) * 4)) & 0xfu;
-            float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 8
-            for (int64_t k = 0; k < K; ++k) {
-                float f[4];
-                Vec4<T>::unpack(stream_load(reinterpret_cast<const V*>(src + k * ld) + v), f);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[e] += f[e];
-            }
-            if (nib) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (nib >> e & 1u) acc[e] = sum_of_sparse_average<T>(acc[e], sparse_divisor, K);
-            }
-            float m[4], b[4] = {0.f, 0.f, 0.f, 0.f};
-            Vec4<M>::unpack(stream_load(reinterpret_cast<const VM*>(master) + v), m);
-            if (has_mom && !op.first_step) Vec4<M>::unpack(stream_load(reinterpret_cast<const VM*>(mom) + v), b);
-            float out[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) out[e] = outer_update(acc[e], m[e], b[e], op);
-            const V o = Vec4<T>::pack(out);
-            const uint32_t i = (uint32_t)(v - lo);
-            store_sc1(reinterpret_cast<VM*>(master) + lo, i, Vec4<M>::pack(m));
-            if (has_mom) store_sc1(reinterpret_cast<VM*>(mom) + lo, i, Vec4<M>::pack(b));
-            for (int64_t j = 0; j < K; ++j) store_sc1(reinterpret_cast<V*>(src + j * ld) + lo, i, o);
-        }
-    } else {
-        chunk_range(n, lo, hi);
-        for (int64_t i = lo + threadIdx.x; i < hi; i += kBlock) {
-            float acc = 0.f;
-#pragma unroll 4
-            for (int64_t k = 0; k < K; ++k) acc += Elem<T>::load(src + k * ld + i);
-            if (bits[i >> 6] >> (i & 63) & 1ull) acc = sum_of_sparse_average<T>(acc, sparse_divisor, K);
-            float m = Elem<M>::load(master + i);
-            float b = (has_mom && !op.first_step) ? Elem<M>::load(mom + i) : 0.f;
-            const float out = outer_update(acc, m, b, op);
-            Elem<M>::store(master + i, m);
-            if (has_mom) Elem<M>::store(mom + i, b);
-            for (int64_t j = 0; j < K; ++j) Elem<T>::store(src + j * ld + i, out);
-        }
-    }
-}
-
 // Placement probe of the fused outer step (no reference counterpart): the exact
-// access pattern of diloco_outer_kernel<float, float, true> -- workgroup b's block
+// access pattern of diloco_outer_kernel<float, float, true, DenseSel> -- workgroup b's block
 // of K replica streams, master and momentum read, the same blocks written through
 // the same stores -- with every value written back unchanged, so a caller can time
 // candidate master/momentum buffers against a live replica set without side
@@ -289,41 +264,27 @@ static int launch_replica_mean(const void* src, int64_t K, int64_t ld_src, const
     return check_launch("ga_replica_mean");
 }
 
-template <typename T, typename M>
-static int launch_diloco(const void* src, int64_t K, int64_t ld_src, int64_t n, void* master,
-                         void* mom, const OuterParams& op, void* dst, int64_t K_out,
-                         int64_t ld_dst, hipStream_t stream) {
+// The outer step's launch; who = the entry point (ga_diloco_outer_masked runs it in
+// place over all K rows with a SparseSel).
+template <typename T, typename M, typename Sel = DenseSel>
+static int launch_diloco(const char* who, const void* src, int64_t K, int64_t ld_src, int64_t n, void* master,
+                         void* mom, const OuterParams& op, void* dst, int64_t K_out, int64_t ld_dst,
+                         hipStream_t stream, Sel sel = Sel{}) {
     const int vb = 4 * (int)sizeof(T);
     const int vm = 4 * (int)sizeof(M);
     const bool vec = (n % 4 == 0) && (ld_src % 4 == 0) && (ld_dst % 4 == 0) &&
                      aligned(src, vb) && aligned(dst, vb) && aligned(master, vm) &&
                      aligned(mom, vm);
     if (vec) {
-        hipLaunchKernelGGL((diloco_outer_kernel<T, M, true>), dim3(chunk_grid(n / 4)),
+        hipLaunchKernelGGL((diloco_outer_kernel<T, M, true, Sel>), dim3(chunk_grid(n / 4)),
                            dim3(kBlock), 0, stream, (const T*)src, K, ld_src, n, (M*)master,
-                           (M*)mom, op, (T*)dst, K_out, ld_dst);
+                           (M*)mom, op, (T*)dst, K_out, ld_dst, sel);
     } else {
-        hipLaunchKernelGGL((diloco_outer_kernel<T, M, false>), dim3(chunk_grid(n)),
+        hipLaunchKernelGGL((diloco_outer_kernel<T, M, false, Sel>), dim3(chunk_grid(n)),
                            dim3(kBlock), 0, stream, (const T*)src, K, ld_src, n, (M*)master,
-                           (M*)mom, op, (T*)dst, K_out, ld_dst);
+                           (M*)mom, op, (T*)dst, K_out, ld_dst, sel);
     }
-    return check_launch("ga_diloco_outer");
-}
-
-template <typename T, typename M>
-static int launch_diloco_masked(void* src, int64_t K, int64_t ld, int64_t n, const uint64_t* bits,
-                                float sparse_divisor, void* master, void* mom, const OuterParams& op,
-                                hipStream_t stream) {
-    const bool vec = (n % 4 == 0) && (ld % 4 == 0) && aligned(src, 4 * (int)sizeof(T)) &&
-                     aligned(master, 4 * (int)sizeof(M)) && aligned(mom, 4 * (int)sizeof(M));
-    if (vec) {
-        hipLaunchKernelGGL((diloco_outer_masked_kernel<T, M, true>), dim3(chunk_grid(n / 4)), dim3(kBlock), 0,
-                           stream, (T*)src, K, ld, n, bits, sparse_divisor, (M*)master, (M*)mom, op);
-    } else {
-        hipLaunchKernelGGL((diloco_outer_masked_kernel<T, M, false>), dim3(chunk_grid(n)), dim3(kBlock), 0,
-                           stream, (T*)src, K, ld, n, bits, sparse_divisor, (M*)master, (M*)mom, op);
-    }
-    return check_launch("ga_diloco_outer_masked");
+    return check_launch(who);
 }
 
 }  // namespace ga
@@ -377,14 +338,14 @@ extern "C" GA_API int ga_diloco_outer(int dtype, const void* src, int64_t K, int
     if (momentum == 0.0f) mom = nullptr;
     switch (dtype) {
         case GA_F32:
-            return launch_diloco<float, float>(src, K, ld_src, n, master, mom, op, dst, K_out, ld_dst,
-                                               stream);
+            return launch_diloco<float, float>("ga_diloco_outer", src, K, ld_src, n, master, mom, op, dst, K_out,
+                                               ld_dst, stream);
         case GA_BF16:
             if (master_f32)
-                return launch_diloco<__hip_bfloat16, float>(src, K, ld_src, n, master, mom, op, dst,
-                                                            K_out, ld_dst, stream);
-            return launch_diloco<__hip_bfloat16, __hip_bfloat16>(src, K, ld_src, n, master, mom, op,
-                                                                 dst, K_out, ld_dst, stream);
+                return launch_diloco<__hip_bfloat16, float>("ga_diloco_outer", src, K, ld_src, n, master, mom, op,
+                                                            dst, K_out, ld_dst, stream);
+            return launch_diloco<__hip_bfloat16, __hip_bfloat16>("ga_diloco_outer", src, K, ld_src, n, master, mom,
+                                                                 op, dst, K_out, ld_dst, stream);
         default:
             set_error("ga_diloco_outer: unknown dtype %d", dtype);
             return GA_EINVAL;
@@ -415,13 +376,14 @@ extern "C" GA_API int ga_diloco_outer_masked(int dtype, void* src, int64_t K, in
     GA_REQUIRE(dtype == GA_F32 || master_f32, "ga_diloco_outer_masked: master and momentum must be fp32");
     OuterParams op{divisor, lr, momentum, dampening, weight_decay, first_step ? 1 : 0, nesterov ? 1 : 0};
     if (momentum == 0.0f) mom = nullptr;
+    const SparseSel sel{bits, sparse_divisor};
+    const char* who = "ga_diloco_outer_masked";
     switch (dtype) {
         case GA_F32:
-            return launch_diloco_masked<float, float>(src, K, ld_src, n, bits, sparse_divisor, master, mom, op,
-                                                      stream);
+            return launch_diloco<float, float>(who, src, K, ld_src, n, master, mom, op, src, K, ld_src, stream, sel);
         case GA_BF16:
-            return launch_diloco_masked<__hip_bfloat16, float>(src, K, ld_src, n, bits, sparse_divisor, master,
-                                                               mom, op, stream);
+            return launch_diloco<__hip_bfloat16, float>(who, src, K, ld_src, n, master, mom, op, src, K, ld_src,
+                                                        stream, sel);
         default:
             set_error("ga_diloco_outer_masked: unknown dtype %d", dtype);
             return GA_EINVAL;

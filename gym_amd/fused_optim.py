@@ -56,12 +56,15 @@ PLACEMENT_ROW_PATIENCE = 3
 PLACEMENT_ROW_BUDGET_S = 0.25
 
 
+def _fp32_arena(arena):
+    """True for an fp32 arena that has a gradient set (what both fused optimizers step)."""
+    grads = getattr(arena, "grad_set", None) if hasattr(arena, "grad_set") else getattr(arena, "grad_flat", None)
+    return arena is not None and grads is not None and arena.dtype == torch.float32
+
+
 def fusable(spec_cls, kwargs, arena):
     """True when OptimSpec(spec_cls, **kwargs) can run as ArenaAdam on this arena."""
-    if spec_cls not in (torch.optim.AdamW, torch.optim.Adam):
-        return False
-    grads = getattr(arena, "grad_set", None) if hasattr(arena, "grad_set") else getattr(arena, "grad_flat", None)
-    if arena is None or grads is None or arena.dtype != torch.float32:
+    if spec_cls not in (torch.optim.AdamW, torch.optim.Adam) or not _fp32_arena(arena):
         return False
     kw = dict(kwargs or {})
     if any(kw.get(k) for k in _UNSUPPORTED):
@@ -130,7 +133,103 @@ def place_moment_rows(P, G, Mr, Vr, max_candidates=None, max_frac=None, patience
     return outM, outV, bufs, watch.stamp(rec)
 
 
-class ArenaAdam(torch.optim.Optimizer):
+class _ArenaOptimizer(torch.optim.Optimizer):
+    """What ArenaAdam and ArenaSGD share: the binding to one node's ParamArena or
+    a ReplicaArena, the clip buffers, the joining of present parameters into
+    launch ranges, and step().  A subclass supplies _ranges (the present
+    parameters under their key: what a launch's scalars depend on), _prepare
+    (what must be in place before launching), _launch and, where a step leaves
+    something per parameter, _finish."""
+
+    def __init__(self, params, defaults, arena):
+        super().__init__(params, defaults)
+        name = type(self).__name__
+        if len(self.param_groups) != 1:
+            raise ValueError(f"{name}: one parameter group (the node's arena)")
+        self.arenas = list(getattr(arena, "arenas", [arena]))
+        self._arena = arena  # P and G are read from it at every use: the sets may be relocated
+        self.K, self.ld = self.P.shape
+        where = {}
+        for k, ar in enumerate(self.arenas):
+            for i, p in enumerate(ar.params):
+                where[id(p)] = (k, ar.layout.offsets[i], ar.layout.numels[i])
+        self._where = where
+        self._spans = [[] for _ in self.arenas]  # per replica: (param, offset, numel) in arena order
+        for p in self.param_groups[0]["params"]:
+            if id(p) not in where:
+                raise ValueError(f"{name}: every parameter must live in the arena")
+            k, o, n = where[id(p)]
+            self._spans[k].append((p, o, n))
+        for sp in self._spans:
+            sp.sort(key=lambda t: t[1])
+        self._partials = ops.sumsq_partials(self.P.device, self.K)
+        self._clip = torch.ones(2 * self.K, dtype=torch.float32, device=self.P.device)
+
+    @property
+    def P(self):
+        """The parameter set [K, ld] (the replica arena's rows, or the node's arena as one row)."""
+        a = self._arena
+        return a.flat_set if hasattr(a, "flat_set") else a.flat.view(1, -1)
+
+    @property
+    def G(self):
+        """The gradient set, read from the arena like P."""
+        a = self._arena
+        return a.grad_set if hasattr(a, "grad_set") else a.grad_flat.view(1, -1)
+
+    def _join(self, live):
+        """live: per replica the (offset, numel, key) spans of its present
+        parameters, sorted.  Returns per replica [(a, b, key)]: the contiguous
+        ranges of present parameters that share the key -- adjacent spans (only
+        zero padding, < 64 elements, between them) joined, and the whole row
+        when all of a replica are present on one key: the padding stays 0."""
+        ranges = []
+        for k, spans in enumerate(live):
+            out = []
+            for o, n, key in spans:
+                if out and o - out[-1][1] < 64 and out[-1][2] == key:
+                    out[-1][1] = o + n
+                else:
+                    out.append([o, o + n, key])
+            if len(out) == 1 and len(spans) == len(self._spans[k]):
+                out = [[0, self.ld, out[0][2]]]
+            ranges.append([tuple(r) for r in out])
+        return ranges
+
+    _whole_set = True  # one launch may cover the [K, ld] sets when every replica has the same whole-row range
+
+    def _finish(self):
+        pass
+
+    @torch.no_grad()
+    def step(self, closure=None, max_norm=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        ranges = self._ranges()
+        for ar in self.arenas:
+            ar.sync_grads()
+        if not any(ranges):  # no parameter has a gradient: torch's step does nothing
+            return loss
+        self._prepare()
+        clip = None
+        if max_norm:
+            ops.grad_clip_coef(self.G, self.ld, max_norm, self._partials, self._clip)
+            clip = self._clip
+        whole = ranges[0]
+        if self._whole_set and whole and whole[0][:2] == (0, self.ld) and all(r == whole for r in ranges):
+            self._launch(None, 0, self.ld, whole[0][2], clip)
+        else:
+            for k in range(self.K):  # per replica: partial ranges, keys apart, or state rows placed apart
+                ck = clip[2 * k:2 * k + 2] if clip is not None else None
+                for a, b, key in ranges[k]:
+                    self._launch(k, a, b, key, ck)
+        self._finish()
+        return loss
+
+
+class ArenaAdam(_ArenaOptimizer):
     """Adam/AdamW over one node's ParamArena, or over a ReplicaArena (K nodes of
     one process, [K, ld] parameter/gradient sets: one launch for all of them,
     each replica clipped by its own gradient norm)."""
@@ -151,13 +250,7 @@ class ArenaAdam(torch.optim.Optimizer):
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False,
                         maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
                         decoupled_weight_decay=bool(decoupled))
-        super().__init__(params, defaults)
-        if len(self.param_groups) != 1:
-            raise ValueError("ArenaAdam: one parameter group (the node's arena)")
-        self.arenas = list(getattr(arena, "arenas", [arena]))
-        self._arena = arena  # P and G are read from it at every use: the sets may be relocated
-        self.K, self.ld = self.P.shape
-        dev = self.P.device
+        super().__init__(params, defaults, arena)
         self._M = torch.zeros_like(self.P, dtype=torch.float32)
         self._V = torch.zeros_like(self.P, dtype=torch.float32)
         # per replica [ld] rows of the moments: views of _M / _V, or (after a per-replica
@@ -168,40 +261,14 @@ class ArenaAdam(torch.optim.Optimizer):
         # share a count -- state[p]["step"] of its members IS the group's tensor, so a step advances a
         # group with one add.  One group while every parameter has had a gradient on every step.
         self._groups = [[torch.tensor(0.0), []]]
-        where = {}
-        for k, ar in enumerate(self.arenas):
-            for i, p in enumerate(ar.params):
-                where[id(p)] = (k, ar.layout.offsets[i], ar.layout.numels[i])
-        self._spans = [[] for _ in self.arenas]  # per replica: (param, offset, numel) in arena order
-        self._where = where
         for p in self.param_groups[0]["params"]:
-            if id(p) not in where:
-                raise ValueError("ArenaAdam: every parameter must live in the arena")
-            k, o, n = where[id(p)]
-            self._spans[k].append((p, o, n))
-            self._groups[0][1].append((p, k, o, n))
+            self._groups[0][1].append((p, *self._where[id(p)]))
             self._bind_state(p)
-        for sp in self._spans:
-            sp.sort(key=lambda t: t[1])
-        self._partials = ops.sumsq_partials(dev, self.K)
-        self._clip = torch.ones(2 * self.K, dtype=torch.float32, device=dev)
         self._placed = None  # the candidate buffer holding M and V once _place chose one
         self._placed_for = None  # (P, G) data pointers the moments were placed against
         self._placements = 0  # searches run (a relocated P / G set is searched again)
         self.placement = None  # the placement record (probe times, or why it was skipped)
         self.place_opt = placement  # False: never probe / move the moments (gym_amd.placement.policy)
-
-    @property
-    def P(self):
-        """The parameter set [K, ld] (the replica arena's rows, or the node's arena as one row)."""
-        a = self._arena
-        return a.flat_set if hasattr(a, "flat_set") else a.flat.view(1, -1)
-
-    @property
-    def G(self):
-        """The gradient set, read from the arena like P."""
-        a = self._arena
-        return a.grad_set if hasattr(a, "grad_set") else a.grad_flat.view(1, -1)
 
     @property
     def M(self):
@@ -337,40 +404,26 @@ class ArenaAdam(torch.optim.Optimizer):
             torch.cuda.empty_cache()
         self.placement = rec
 
-    @torch.no_grad()
-    def step(self, closure=None, max_norm=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        ranges = self._advance()
-        for ar in self.arenas:
-            ar.sync_grads()
-        if not any(ranges):  # no parameter has a gradient: torch's step does nothing
-            return loss
+    @property
+    def _whole_set(self):
+        return self._M is not None  # rows placed apart take one launch each
+
+    def _prepare(self):
         if self._placed_for != (self.P.data_ptr(), self.G.data_ptr()):
             self._place()
-        clip = None
-        if max_norm:
-            ops.grad_clip_coef(self.G, self.ld, max_norm, self._partials, self._clip)
-            clip = self._clip
-        whole = ranges[0]
-        if self._M is not None and whole and whole[0][:2] == (0, self.ld) and all(r == whole for r in ranges):
-            ops.adam_step(self.P, self.G, self._M, self._V, clip_coef=clip, **self._hp(whole[0][2]))
-            return loss
-        hps = {}
-        for k in range(self.K):  # per replica (its moments placed apart, partial ranges, or counts apart)
-            ck = clip[2 * k:2 * k + 2] if clip is not None else None
-            for a, b, t in ranges[k]:
-                hp = hps.get(t) or hps.setdefault(t, self._hp(t))
-                ops.adam_step(self.P[k, a:b], self.G[k, a:b], self._Mr[k][a:b], self._Vr[k][a:b], clip_coef=ck, **hp)
-        return loss
+        self._hps = {}  # the launch scalars per count of this step
 
-    def _advance(self):
+    def _launch(self, k, a, b, t, clip):
+        hp = self._hps.get(t) or self._hps.setdefault(t, self._hp(t))
+        if k is None:
+            ops.adam_step(self.P, self.G, self._M, self._V, clip_coef=clip, **hp)
+        else:
+            ops.adam_step(self.P[k, a:b], self.G[k, a:b], self._Mr[k][a:b], self._Vr[k][a:b], clip_coef=clip, **hp)
+
+    def _ranges(self):
         """Advance the count of every parameter that has a gradient now and
         return, per replica, [(a, b, t)]: the contiguous ranges of present
-        parameters that share the count t (the whole row when all of a replica
-        are present on one count: the padding stays 0).  A group whose members
+        parameters that share the count t (_join).  A group whose members
         are all present advances with one add; one that is partly present
         splits; groups that reach the same count become one again."""
         groups = self._groups
@@ -399,19 +452,7 @@ class ArenaAdam(torch.optim.Optimizer):
                     for m in ms:
                         self.state[m[0]]["step"] = into[0]
         self._groups = list(merged.values())
-        ranges = []
-        for k, spans in enumerate(live):
-            spans.sort()
-            out = []
-            for o, n, t in spans:
-                if out and o - out[-1][1] < 64 and out[-1][2] == t:  # adjacent (zero padding between), same count
-                    out[-1][1] = o + n
-                else:
-                    out.append([o, o + n, t])
-            if len(out) == 1 and len(spans) == len(self._spans[k]):
-                out = [[0, self.ld, out[0][2]]]
-            ranges.append([tuple(r) for r in out])
-        return ranges
+        return self._join([sorted(spans) for spans in live])
 
     def _hp(self, t):
         """The launch scalars of a step at count t (torch's _single_tensor_adam)."""
@@ -432,10 +473,7 @@ def fusable_sgd(spec_cls, kwargs, arena):
     """True when OptimSpec(spec_cls, **kwargs) can run as ArenaSGD on this arena:
     torch.optim.SGD on an fp32 arena with a gradient set, no maximize /
     differentiable, a float learning rate."""
-    if spec_cls is not torch.optim.SGD:
-        return False
-    grads = getattr(arena, "grad_set", None) if hasattr(arena, "grad_set") else getattr(arena, "grad_flat", None)
-    if arena is None or grads is None or arena.dtype != torch.float32:
+    if spec_cls is not torch.optim.SGD or not _fp32_arena(arena):
         return False
     kw = dict(kwargs or {})
     if kw.get("maximize") or kw.get("differentiable"):
@@ -445,7 +483,7 @@ def fusable_sgd(spec_cls, kwargs, arena):
     return not isinstance(kw.get("lr", 1e-3), torch.Tensor)
 
 
-class ArenaSGD(torch.optim.Optimizer):
+class ArenaSGD(_ArenaOptimizer):
     """torch.optim.SGD (momentum, dampening, Nesterov, L2 weight decay) over one
     node's ParamArena or a ReplicaArena, built as ArenaAdam is: step() is one
     ga_sgd_step launch over the [K, ld] sets (read p, g, buf; write p, buf) and,
@@ -476,37 +514,13 @@ class ArenaSGD(torch.optim.Optimizer):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
                         maximize=False, foreach=None, differentiable=False, fused=None)
-        super().__init__(params, defaults)
-        if len(self.param_groups) != 1:
-            raise ValueError("ArenaSGD: one parameter group (the node's arena)")
-        self.arenas = list(getattr(arena, "arenas", [arena]))
-        self._arena = arena  # P and G are read from it at every use: the sets may be relocated
-        self.K, self.ld = self.P.shape
-        where = {}
-        for k, ar in enumerate(self.arenas):
-            for i, p in enumerate(ar.params):
-                where[id(p)] = (k, ar.layout.offsets[i], ar.layout.numels[i])
-        self._where = where
-        self._spans = [[] for _ in self.arenas]  # per replica: (param, offset, numel) in arena order
-        for p in self.param_groups[0]["params"]:
-            if id(p) not in where:
-                raise ValueError("ArenaSGD: every parameter must live in the arena")
-            k, o, n = where[id(p)]
-            self._spans[k].append((p, o, n))
-        for sp in self._spans:
-            sp.sort(key=lambda t: t[1])
+        super().__init__(params, defaults, arena)
         self._B = None  # the momentum buffer [K, ld], allocated when momentum != 0
         self._owner = None  # keeps a caller's buffer memory alive (move_buffer)
         self._inited = set()  # ids of the parameters whose buffer holds their first gradient
         if momentum != 0:
             self._buffer()
-        dev = self.P.device
-        self._partials = ops.sumsq_partials(dev, self.K)
-        self._clip = torch.ones(2 * self.K, dtype=torch.float32, device=dev)
         self.placement = {"placed": False, "why": "no search for SGD"}
-
-    P = ArenaAdam.P  # the parameter / gradient sets [K, ld], read from the arena at every use
-    G = ArenaAdam.G
 
     @property
     def B(self):
@@ -561,65 +575,45 @@ class ArenaSGD(torch.optim.Optimizer):
                     self._B[k, o:o + n].copy_(loaded[id(p)].reshape(-1))
                 self._bind_state(p)
 
-    @torch.no_grad()
-    def step(self, closure=None, max_norm=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        g = self.param_groups[0]
-        momentum = float(g["momentum"])
-        ranges, fresh = self._ranges(momentum != 0)
-        for ar in self.arenas:
-            ar.sync_grads()
-        if not any(ranges):  # no parameter has a gradient: torch's step does nothing
-            return loss
-        B = self._buffer() if momentum != 0 else None
-        clip = None
-        if max_norm:
-            ops.grad_clip_coef(self.G, self.ld, max_norm, self._partials, self._clip)
-            clip = self._clip
-        # neg_lr and 1 - dampening in double, rounded once (torch's alpha=-lr, alpha=1 - dampening)
-        hp = dict(neg_lr=-float(g["lr"]), momentum=momentum, one_m_dampening=1 - float(g["dampening"]),
-                  weight_decay=float(g["weight_decay"]), nesterov=bool(g["nesterov"]))
-        whole = ranges[0]
-        if whole and whole[0][:2] == (0, self.ld) and all(r == whole for r in ranges):
-            ops.sgd_step(self.P, self.G, B, first=whole[0][2], clip_coef=clip, **hp)
-        else:
-            for k in range(self.K):  # per replica: partial ranges, or flags apart
-                ck = clip[2 * k:2 * k + 2] if clip is not None else None
-                for a, b, first in ranges[k]:
-                    ops.sgd_step(self.P[k, a:b], self.G[k, a:b], B[k, a:b] if B is not None else None, first=first,
-                                 clip_coef=ck, **hp)
-        for p in fresh:  # their buffers now hold their first gradient
-            self._inited.add(id(p))
-            self._bind_state(p)
-        return loss
-
-    def _ranges(self, with_momentum):
+    def _ranges(self):
         """Per replica [(a, b, first)]: the contiguous ranges of present parameters
-        that share the flag (adjacent spans joined across the zero padding; the
-        whole row when all of a replica are present on one flag), and the list of
-        present parameters that are not initialised yet.  Without momentum there
-        is no buffer and no flag (torch creates none)."""
-        ranges, fresh = [], []
-        for k, spans in enumerate(self._spans):
-            out, present = [], 0
+        that share the flag (_join); self._fresh lists the present parameters
+        that are not initialised yet.  Without momentum there is no buffer and no
+        flag (torch creates none)."""
+        with_momentum = float(self.param_groups[0]["momentum"]) != 0
+        live, self._fresh = [], []
+        for spans in self._spans:
+            live.append([])
             for p, o, n in spans:
                 if p.grad is None:
                     continue
-                present += 1
                 first = with_momentum and id(p) not in self._inited
                 if first:
-                    fresh.append(p)
-                if out and o - out[-1][1] < 64 and out[-1][2] == first:  # adjacent (zero padding between), same flag
-                    out[-1][1] = o + n
-                else:
-                    out.append([o, o + n, first])
-            if len(out) == 1 and present == len(spans):
-                out = [[0, self.ld, out[0][2]]]
-            ranges.append([tuple(r) for r in out])
-        return ranges, fresh
+                    self._fresh.append(p)
+                live[-1].append((o, n, first))
+        return self._join(live)
+
+    def _prepare(self):
+        g = self.param_groups[0]
+        # neg_lr and 1 - dampening in double, rounded once (torch's alpha=-lr, alpha=1 - dampening)
+        self._hp = dict(neg_lr=-float(g["lr"]), momentum=float(g["momentum"]),
+                        one_m_dampening=1 - float(g["dampening"]), weight_decay=float(g["weight_decay"]),
+                        nesterov=bool(g["nesterov"]))
+        if self._hp["momentum"] != 0:
+            self._buffer()
+
+    def _launch(self, k, a, b, first, clip):
+        B = self._B if self._hp["momentum"] != 0 else None
+        if k is None:
+            ops.sgd_step(self.P, self.G, B, first=first, clip_coef=clip, **self._hp)
+        else:
+            ops.sgd_step(self.P[k, a:b], self.G[k, a:b], B[k, a:b] if B is not None else None, first=first,
+                         clip_coef=clip, **self._hp)
+
+    def _finish(self):
+        for p in self._fresh:  # their buffers now hold their first gradient
+            self._inited.add(id(p))
+            self._bind_state(p)
 
 
 FUSED = (ArenaAdam, ArenaSGD)  # the inner optimizers whose step(max_norm=) clips on the device

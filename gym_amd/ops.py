@@ -519,15 +519,23 @@ def probe_mean_placement(reps, n):
     check(lib().ga_probe_mean_placement(_p(r2), K, ld, int(n), _stream()), "ga_probe_mean_placement")
 
 
-def probe_adam_placement(param, grad, exp_avg, exp_avg_sq):
-    """ga_adam_step's access pattern over fp32 [K, ld] sets of one layout, every
-    value written back unchanged (placement probe)."""
-    ts = [_as2d(t) for t in (param, grad, exp_avg, exp_avg_sq)]
-    _gpu(*ts)
+def _one_layout(tensors, clip_coef, message):
+    """(2-D views, K, ld) of the fp32 [K, ld] replica sets (or 1-D buffers) of one
+    layout that an inner-optimizer pass streams; `message` when they are not."""
+    ts = [_as2d(t) for t in tensors]
+    _gpu(*ts, clip_coef)
     K, ld = _rows_ld(ts[0])
     for t in ts:
         if t.dtype != torch.float32 or t.shape != ts[0].shape or t.stride() != ts[0].stride() or t.stride(-1) != 1:
-            raise ValueError("probe_adam_placement: fp32 replica sets of one layout")
+            raise ValueError(message)
+    return ts, K, ld
+
+
+def probe_adam_placement(param, grad, exp_avg, exp_avg_sq):
+    """ga_adam_step's access pattern over fp32 [K, ld] sets of one layout, every
+    value written back unchanged (placement probe)."""
+    ts, K, ld = _one_layout((param, grad, exp_avg, exp_avg_sq), None,
+                            "probe_adam_placement: fp32 replica sets of one layout")
     check(lib().ga_probe_adam_placement(_p(ts[0]), _p(ts[1]), _p(ts[2]), _p(ts[3]), K, ld, ts[0].shape[1],
                                         _stream()), "ga_probe_adam_placement")
 
@@ -553,12 +561,8 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lerp_w, beta2, one_m_beta2, eps,
               bc2_sqrt, clip_coef=None, n=None):
     """One fused Adam/AdamW step over fp32 [K, ld] replica sets (or 1-D buffers)
     of one shape; every replica's first n elements (see include/gym_amd.h)."""
-    ts = [_as2d(t) for t in (param, grad, exp_avg, exp_avg_sq)]
-    _gpu(*ts, clip_coef)
-    K, ld = _rows_ld(ts[0])
-    for t in ts:
-        if t.dtype != torch.float32 or t.shape != ts[0].shape or t.stride() != ts[0].stride() or t.stride(-1) != 1:
-            raise ValueError("adam_step: param/grad/exp_avg/exp_avg_sq must be fp32 replica sets of one layout")
+    ts, K, ld = _one_layout((param, grad, exp_avg, exp_avg_sq), clip_coef,
+                            "adam_step: param/grad/exp_avg/exp_avg_sq must be fp32 replica sets of one layout")
     n = ts[0].shape[1] if n is None else int(n)
     if clip_coef is not None and clip_coef.numel() < 2 * K:
         raise ValueError("adam_step: clip_coef must hold 2 floats per replica")
@@ -574,12 +578,8 @@ def sgd_step(param, grad, buf, *, neg_lr, momentum, one_m_dampening, weight_deca
     momentum buffer, None only with momentum == 0."""
     if buf is None and momentum != 0:
         raise ValueError("sgd_step: a momentum buffer is required with momentum != 0")
-    ts = [_as2d(t) for t in (param, grad) + ((buf,) if buf is not None else ())]
-    _gpu(*ts, clip_coef)
-    K, ld = _rows_ld(ts[0])
-    for t in ts:
-        if t.dtype != torch.float32 or t.shape != ts[0].shape or t.stride() != ts[0].stride() or t.stride(-1) != 1:
-            raise ValueError("sgd_step: param/grad/buf must be fp32 replica sets of one layout")
+    ts, K, ld = _one_layout((param, grad) + ((buf,) if buf is not None else ()), clip_coef,
+                            "sgd_step: param/grad/buf must be fp32 replica sets of one layout")
     n = ts[0].shape[1] if n is None else int(n)
     if n < 0 or n > ts[0].shape[1]:
         raise ValueError("sgd_step: n exceeds the row length (ld < n)")
