@@ -13,7 +13,13 @@
 // depend on the launch geometry.  dst may alias src (in-place average): each
 // lane reads every replica of its vector before it writes any, and no two
 // lanes touch the same vector, so the sources carry no __restrict__.
+//
+// The outer step exists twice: diloco_outer_kernel (SGD / Nesterov on the
+// pseudo-gradient, ga_diloco_outer[_masked]) and diloco_outer_adam_kernel (Adam /
+// AdamW, ga_diloco_outer_adam[_masked]: one more fp32 state stream, adam_math.h's
+// element update).  They share the geometry, the selectors and the helpers below.
 #include "ga_common.h"
+#include "adam_math.h"
 
 namespace ga {
 
@@ -198,6 +204,81 @@ __global__ __launch_bounds__(kBlock) void diloco_outer_kernel(
     }
 }
 
+// The outer step with an Adam/AdamW update (ga_diloco_outer_adam[_masked]): the
+// geometry, loads, stores and selectors of diloco_outer_kernel, one more fp32 state
+// stream, adam_elem (adam_math.h, the inner optimizer's element update) on the
+// pseudo-gradient master - avg.  Master and both moments are fp32; zero moments with
+// the bias corrections of t = 1 give torch's first step, so there is no first flag.
+// A sibling rather than an update functor of diloco_outer_kernel, so that kernel's
+// machine code stays what the headline measurement ran.
+template <typename T, bool VEC, typename Sel>
+__global__ __launch_bounds__(kBlock) void diloco_outer_adam_kernel(
+    const T* src, int64_t K, int64_t ld_src, int64_t n, float divisor, float* master, float* exp_avg,
+    float* exp_avg_sq, AdamParams ap, T* dst, int64_t K_out, int64_t ld_dst, Sel sel) {
+    constexpr bool kSparse = !std::is_same<Sel, DenseSel>::value;
+    if constexpr (kSparse) {  // in place over all K rows, as ga_diloco_outer_adam_masked requires
+        dst = const_cast<T*>(src);
+        K_out = K;
+        ld_dst = ld_src;
+    }
+    int64_t lo, hi;
+    if constexpr (VEC) {
+        using V = typename Vec4<T>::type;
+        chunk_range(n >> 2, lo, hi);
+        for (int64_t v = lo + threadIdx.x; v < hi; v += kBlock) {
+            uint32_t nib = 0;
+            if constexpr (kSparse) nib = sel.nibble(v);
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8
+            for (int64_t k = 0; k < K; ++k) {
+                float f[4];
+                Vec4<T>::unpack(stream_load(reinterpret_cast<const V*>(src + k * ld_src) + v), f);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e] += f[e];
+            }
+            if constexpr (kSparse) {
+                if (nib) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (nib >> e & 1u) acc[e] = sum_of_sparse_average<T>(acc[e], sel.sparse_divisor, K);
+                }
+            }
+            float p[4], m[4], s[4];
+            Vec4<float>::unpack(stream_load(reinterpret_cast<const float4*>(master) + v), p);
+            Vec4<float>::unpack(stream_load(reinterpret_cast<const float4*>(exp_avg) + v), m);
+            Vec4<float>::unpack(stream_load(reinterpret_cast<const float4*>(exp_avg_sq) + v), s);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float g = p[e] - acc[e] / divisor;
+                adam_elem(p[e], g, m[e], s[e], ap);
+            }
+            const V o = Vec4<T>::pack(p);
+            const uint32_t i = (uint32_t)(v - lo);
+            store_sc1(reinterpret_cast<float4*>(master) + lo, i, Vec4<float>::pack(p));
+            store_sc1(reinterpret_cast<float4*>(exp_avg) + lo, i, Vec4<float>::pack(m));
+            store_sc1(reinterpret_cast<float4*>(exp_avg_sq) + lo, i, Vec4<float>::pack(s));
+            for (int64_t j = 0; j < K_out; ++j) store_sc1(reinterpret_cast<V*>(dst + j * ld_dst) + lo, i, o);
+        }
+    } else {
+        chunk_range(n, lo, hi);
+        for (int64_t i = lo + threadIdx.x; i < hi; i += kBlock) {
+            float acc = 0.f;
+#pragma unroll 4
+            for (int64_t k = 0; k < K; ++k) acc += Elem<T>::load(src + k * ld_src + i);
+            if constexpr (kSparse) {
+                if (sel.bit(i)) acc = sum_of_sparse_average<T>(acc, sel.sparse_divisor, K);
+            }
+            float p = master[i], m = exp_avg[i], s = exp_avg_sq[i];
+            float g = p - acc / divisor;
+            adam_elem(p, g, m, s, ap);
+            master[i] = p;
+            exp_avg[i] = m;
+            exp_avg_sq[i] = s;
+            for (int64_t j = 0; j < K_out; ++j) Elem<T>::store(dst + j * ld_dst + i, p);
+        }
+    }
+}
+
 // Placement probe of the fused outer step (no reference counterpart): the exact
 // access pattern of diloco_outer_kernel<float, float, true, DenseSel> -- workgroup b's block
 // of K replica streams, master and momentum read, the same blocks written through
@@ -283,6 +364,26 @@ static int launch_diloco(const char* who, const void* src, int64_t K, int64_t ld
         hipLaunchKernelGGL((diloco_outer_kernel<T, M, false, Sel>), dim3(chunk_grid(n)),
                            dim3(kBlock), 0, stream, (const T*)src, K, ld_src, n, (M*)master,
                            (M*)mom, op, (T*)dst, K_out, ld_dst, sel);
+    }
+    return check_launch(who);
+}
+
+// The Adam outer step's launch; state is fp32 whatever the arena's dtype.
+template <typename T, typename Sel = DenseSel>
+static int launch_diloco_adam(const char* who, const void* src, int64_t K, int64_t ld_src, int64_t n, float divisor,
+                              float* master, float* exp_avg, float* exp_avg_sq, const AdamParams& ap, void* dst,
+                              int64_t K_out, int64_t ld_dst, hipStream_t stream, Sel sel = Sel{}) {
+    const int vb = 4 * (int)sizeof(T);
+    const bool vec = (n % 4 == 0) && (ld_src % 4 == 0) && (ld_dst % 4 == 0) && aligned(src, vb) &&
+                     aligned(dst, vb) && aligned(master, 16) && aligned(exp_avg, 16) && aligned(exp_avg_sq, 16);
+    if (vec) {
+        hipLaunchKernelGGL((diloco_outer_adam_kernel<T, true, Sel>), dim3(chunk_grid(n / 4)), dim3(kBlock), 0,
+                           stream, (const T*)src, K, ld_src, n, divisor, master, exp_avg, exp_avg_sq, ap, (T*)dst,
+                           K_out, ld_dst, sel);
+    } else {
+        hipLaunchKernelGGL((diloco_outer_adam_kernel<T, false, Sel>), dim3(chunk_grid(n)), dim3(kBlock), 0, stream,
+                           (const T*)src, K, ld_src, n, divisor, master, exp_avg, exp_avg_sq, ap, (T*)dst, K_out,
+                           ld_dst, sel);
     }
     return check_launch(who);
 }
@@ -386,6 +487,71 @@ extern "C" GA_API int ga_diloco_outer_masked(int dtype, void* src, int64_t K, in
                                                         stream, sel);
         default:
             set_error("ga_diloco_outer_masked: unknown dtype %d", dtype);
+            return GA_EINVAL;
+    }
+}
+
+extern "C" GA_API int ga_diloco_outer_adam(int dtype, const void* src, int64_t K, int64_t ld_src, int64_t n,
+                                           float divisor, float* master, float* exp_avg, float* exp_avg_sq,
+                                           float lerp_w, float beta2, float one_m_beta2, float eps, float wd_factor,
+                                           float l2_wd, float step_size, float bc2_sqrt, void* dst, int64_t K_out,
+                                           int64_t ld_dst, hipStream_t stream) {
+    clear_error();
+    GA_REQUIRE(n >= 0 && K >= 1 && K_out >= 0, "ga_diloco_outer_adam: bad sizes n=%lld K=%lld K_out=%lld",
+               (long long)n, (long long)K, (long long)K_out);
+    if (n == 0) return GA_OK;
+    GA_REQUIRE(src && master, "ga_diloco_outer_adam: null src/master");
+    GA_REQUIRE(exp_avg && exp_avg_sq, "ga_diloco_outer_adam: null exp_avg/exp_avg_sq");
+    GA_REQUIRE(K_out == 0 || dst, "ga_diloco_outer_adam: null dst");
+    GA_REQUIRE(K == 1 || ld_src >= n, "ga_diloco_outer_adam: ld_src < n");
+    GA_REQUIRE(K_out <= 1 || ld_dst >= n, "ga_diloco_outer_adam: ld_dst < n");
+    GA_REQUIRE(divisor != 0.0f, "ga_diloco_outer_adam: divisor is 0");
+    const AdamParams ap{lerp_w, beta2, one_m_beta2, eps, wd_factor, l2_wd, step_size, bc2_sqrt};
+    const char* who = "ga_diloco_outer_adam";
+    switch (dtype) {
+        case GA_F32:
+            return launch_diloco_adam<float>(who, src, K, ld_src, n, divisor, master, exp_avg, exp_avg_sq, ap, dst,
+                                             K_out, ld_dst, stream);
+        case GA_BF16:
+            return launch_diloco_adam<__hip_bfloat16>(who, src, K, ld_src, n, divisor, master, exp_avg, exp_avg_sq,
+                                                      ap, dst, K_out, ld_dst, stream);
+        default:
+            set_error("ga_diloco_outer_adam: unknown dtype %d", dtype);
+            return GA_EINVAL;
+    }
+}
+
+extern "C" GA_API int ga_diloco_outer_adam_masked(int dtype, void* src, int64_t K, int64_t ld_src, int64_t n,
+                                                  const uint64_t* bits, float sparse_divisor, float divisor,
+                                                  float* master, float* exp_avg, float* exp_avg_sq, float lerp_w,
+                                                  float beta2, float one_m_beta2, float eps, float wd_factor,
+                                                  float l2_wd, float step_size, float bc2_sqrt, void* dst,
+                                                  int64_t K_out, int64_t ld_dst, hipStream_t stream) {
+    clear_error();
+    GA_REQUIRE(n >= 0 && K >= 1, "ga_diloco_outer_adam_masked: bad sizes n=%lld K=%lld", (long long)n, (long long)K);
+    // the sparse average only vanishes into the outer step when that overwrites every row it wrote
+    GA_REQUIRE(dst == src && K_out == K && (K == 1 || ld_dst == ld_src),
+               "ga_diloco_outer_adam_masked: the step must run in place over all K rows (dst == src, K_out == K = "
+               "%lld, ld_dst == ld_src); got K_out=%lld", (long long)K, (long long)K_out);
+    GA_REQUIRE(sparse_divisor > 0.0f, "ga_diloco_outer_adam_masked: sparse_divisor must be > 0");
+    GA_REQUIRE(divisor != 0.0f, "ga_diloco_outer_adam_masked: divisor is 0");
+    if (n == 0) return GA_OK;
+    GA_REQUIRE(bits != nullptr, "ga_diloco_outer_adam_masked: null mask words");
+    GA_REQUIRE(src && master, "ga_diloco_outer_adam_masked: null src/master");
+    GA_REQUIRE(exp_avg && exp_avg_sq, "ga_diloco_outer_adam_masked: null exp_avg/exp_avg_sq");
+    GA_REQUIRE(K == 1 || ld_src >= n, "ga_diloco_outer_adam_masked: ld_src < n");
+    const AdamParams ap{lerp_w, beta2, one_m_beta2, eps, wd_factor, l2_wd, step_size, bc2_sqrt};
+    const SparseSel sel{bits, sparse_divisor};
+    const char* who = "ga_diloco_outer_adam_masked";
+    switch (dtype) {
+        case GA_F32:
+            return launch_diloco_adam<float>(who, src, K, ld_src, n, divisor, master, exp_avg, exp_avg_sq, ap, src,
+                                             K, ld_src, stream, sel);
+        case GA_BF16:
+            return launch_diloco_adam<__hip_bfloat16>(who, src, K, ld_src, n, divisor, master, exp_avg, exp_avg_sq,
+                                                      ap, src, K, ld_src, stream, sel);
+        default:
+            set_error("ga_diloco_outer_adam_masked: unknown dtype %d", dtype);
             return GA_EINVAL;
     }
 }

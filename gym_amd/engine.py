@@ -9,6 +9,7 @@ node count is K_total = world * K_local.
 
   MeanReduce   SimpleReduce grads, FedAvg params     strategy.py:128-142, federated_averaging.py:53-69
   DiLoCoOuter  fused outer SGD/Nesterov step        diloco.py:34-76
+  DiLoCoOuterAdam  the same with an Adam/AdamW update  diloco.py:26-28
   Sparta       sparse average (Philox or mask)      sparta.py:24-44
   DeMoCodec    DCT encode/top-k + gather + decode   demo_impl/demo.py:142-209
 """
@@ -259,10 +260,7 @@ class DiLoCoOuter:
         else:
             self.plan = None
             self.per = self.n
-        # master and momentum in one allocation (a placement candidate, see _place)
-        self._state = torch.zeros((2 if momentum != 0 else 1) * self.per, device=device, dtype=torch.float32)
-        self.master = self._state[:self.per]
-        self.mom = self._state[self.per:] if momentum != 0 else None
+        self._alloc_state(device)
         self.placement = None  # the placement probe's record (bench / DESIGN)
         self._placed_for = None
         self._placed = None  # the candidate buffer holding the state, when one was chosen
@@ -275,6 +273,13 @@ class DiLoCoOuter:
         self.sum = torch.empty(n, device=device, dtype=dtype) if (X and not self.shard) else None
         self.rs_out = torch.empty(self.per, device=device, dtype=dtype) if self.shard else None
         self.launch_elems = []  # elements per ga_diloco_outer launch of the last step (bench roofline)
+
+    def _alloc_state(self, device):
+        # master and momentum in one allocation (a placement candidate, see _place)
+        momentum = self.hp["momentum"]
+        self._state = torch.zeros((2 if momentum != 0 else 1) * self.per, device=device, dtype=torch.float32)
+        self.master = self._state[:self.per]
+        self.mom = self._state[self.per:] if momentum != 0 else None
 
     def init_master(self, params_flat):
         """master <- the node's initial parameters (diloco.py:81-82)."""
@@ -291,6 +296,13 @@ class DiLoCoOuter:
         ops.diloco_outer(src, self.master[m0:m1], mom, dst, m1 - m0, divisor, h["lr"], h["momentum"],
                          h["dampening"], h["weight_decay"], h["nesterov"], self.first)
         self.launch_elems.append(m1 - m0)
+
+    def _outer_masked(self, reps, sparse_mask):
+        h, n = self.hp, self.n
+        ops.diloco_outer_masked(reps[:, :n], sparse_mask, self.master, self.mom, n, float(self.K_total),
+                                self.K_total, h["lr"], h["momentum"], h["dampening"], h["weight_decay"],
+                                h["nesterov"], self.first)
+        self.launch_elems.append(n)
 
     def _outer_shard(self, rs_shard, m, own):
         self._outer(rs_shard, self.K_total, own, m[0], m[1])
@@ -397,11 +409,7 @@ class DiLoCoOuter:
                 raise ValueError("DiLoCoOuter: the masked outer step needs a local (no-exchange) step; run Sparta "
                                  "and the outer step one after the other")
             reps = self._place(reps)
-            h = self.hp
-            ops.diloco_outer_masked(reps[:, :n], sparse_mask, self.master, self.mom, n, float(self.K_total),
-                                    self.K_total, h["lr"], h["momentum"], h["dampening"], h["weight_decay"],
-                                    h["nesterov"], self.first)
-            self.launch_elems.append(n)
+            self._outer_masked(reps, sparse_mask)
         elif not self.coll.exchange:  # one kernel: read every replica, update, write every replica
             reps = self._place(reps)
             self._outer(reps[:, :n], self.K_total, reps[:, :n])
@@ -412,6 +420,67 @@ class DiLoCoOuter:
         else:
             self.plan.run(self.coll, reps[:, :n], self.rs_out, self._outer_shard)
         self.first = False
+
+
+class DiLoCoOuterAdam(DiLoCoOuter):
+    """DiLoCoOuter for an Adam / AdamW outer optimizer: the same four branches
+    (local in place, the masked boundary step, gloo, RCCL sharded through
+    ShardPlan.run) around ga_diloco_outer_adam.  Master, exp_avg and exp_avg_sq
+    are fp32 in one allocation of 3 * per (per = n / world when sharded); the
+    engine counts the outer steps (t) and hands the kernel torch's bias
+    corrections, computed in Python doubles as ArenaAdam does.  `mom` is None
+    and `hp` holds Adam's hyper-parameters; there is no placement search (the
+    probe kernel models two state streams, this step has three)."""
+
+    def __init__(self, coll: Collective, K_local, n, device, dtype, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                 weight_decay=0.0, decoupled=False, shard=None, chunks=None, placement=True):
+        super().__init__(coll, K_local, n, device, dtype, lr=lr, momentum=0.0, nesterov=False,
+                         weight_decay=weight_decay, shard=shard, chunks=chunks, placement=placement)
+        self.hp = dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps),
+                       weight_decay=float(weight_decay), decoupled=bool(decoupled))
+        self.t = 0  # outer steps taken
+
+    def _alloc_state(self, device):
+        per = self.per
+        self._state = torch.zeros(3 * per, device=device, dtype=torch.float32)
+        self.master, self.exp_avg, self.exp_avg_sq = (self._state[i * per:(i + 1) * per] for i in range(3))
+        self.mom = None
+
+    def init_master(self, params_flat):
+        super().init_master(params_flat)
+        self.t = 0
+        self._state[self.per:].zero_()
+
+    def scalars(self, t):
+        """ga_diloco_outer_adam's scalars at outer step t (torch's _single_tensor_adam)."""
+        h = self.hp
+        lr, (b1, b2), wd = h["lr"], h["betas"], h["weight_decay"]
+        return dict(lerp_w=1 - b1, beta2=b2, one_m_beta2=1 - b2, eps=h["eps"],
+                    wd_factor=(1 - lr * wd) if (h["decoupled"] and wd != 0) else 1.0,
+                    l2_wd=wd if (not h["decoupled"] and wd != 0) else 0.0,
+                    step_size=-(lr / (1 - b1 ** t)), bc2_sqrt=math.sqrt(1 - b2 ** t))
+
+    def _place(self, reps):
+        if self.placement is None:
+            self.placement = {"placed": False, "why": "no search for the Adam outer step (three state streams)"}
+        return reps
+
+    def _outer(self, src, divisor, dst, m0=0, m1=None):
+        m1 = self.per if m1 is None else m1
+        ops.diloco_outer_adam(src, self.master[m0:m1], self.exp_avg[m0:m1], self.exp_avg_sq[m0:m1], dst, m1 - m0,
+                              divisor, **self._scalars)
+        self.launch_elems.append(m1 - m0)
+
+    def _outer_masked(self, reps, sparse_mask):
+        n = self.n
+        ops.diloco_outer_adam_masked(reps[:, :n], sparse_mask, self.master, self.exp_avg, self.exp_avg_sq, n,
+                                     float(self.K_total), self.K_total, **self._scalars)
+        self.launch_elems.append(n)
+
+    def __call__(self, reps, sparse_mask=None):
+        self._scalars = self.scalars(self.t + 1)
+        super().__call__(reps, sparse_mask)
+        self.t += 1
 
 
 def sparta_capacity(n, p):

@@ -183,6 +183,62 @@ def diloco_outer_masked(reps, bits, master, mom, n, sparse_divisor, divisor, lr,
                                        _p(r2), K, ld, _stream()), "ga_diloco_outer_masked")
 
 
+def _adam_scalars(lerp_w, beta2, one_m_beta2, eps, wd_factor, l2_wd, step_size, bc2_sqrt):
+    return tuple(float(x) for x in (lerp_w, beta2, one_m_beta2, eps, wd_factor, l2_wd, step_size, bc2_sqrt))
+
+
+def _adam_state(who, n, master, exp_avg, exp_avg_sq):
+    for t in (master, exp_avg, exp_avg_sq):
+        if t is None:
+            raise ValueError(f"{who}: master, exp_avg and exp_avg_sq are required")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{who}: master, exp_avg and exp_avg_sq must be float32")
+        if t.numel() < n or not t.is_contiguous():
+            raise ValueError(f"{who}: buffers shorter than n")
+
+
+def diloco_outer_adam(src, master, exp_avg, exp_avg_sq, dst, n, divisor, *, lerp_w, beta2, one_m_beta2, eps,
+                      wd_factor, l2_wd, step_size, bc2_sqrt):
+    """Fused DiLoCo outer step with an Adam/AdamW update over [0, n) of the fp32
+    master / exp_avg / exp_avg_sq (ga_diloco_outer_adam; the scalars of adam_step)."""
+    src2 = _as2d(src)
+    dst2 = _as2d(dst) if dst is not None else None
+    _gpu(src2, master, exp_avg, exp_avg_sq, dst2)
+    K, lds = _rows_ld(src2)
+    Ko, ldd = _rows_ld(dst2) if dst2 is not None else (0, 0)
+    _adam_state("diloco_outer_adam", n, master, exp_avg, exp_avg_sq)
+    if src2.shape[1] < n:
+        raise ValueError("diloco_outer_adam: buffers shorter than n")
+    if dst2 is not None and dst2.shape[1] < n:
+        raise ValueError("diloco_outer_adam: dst shorter than n")
+    if dst2 is not None and dst2.dtype != src2.dtype:
+        raise TypeError("diloco_outer_adam: src/dst dtype mismatch")
+    check(lib().ga_diloco_outer_adam(_dtype_code(src2), _p(src2), K, lds, int(n), float(divisor), _p(master),
+                                     _p(exp_avg), _p(exp_avg_sq),
+                                     *_adam_scalars(lerp_w, beta2, one_m_beta2, eps, wd_factor, l2_wd, step_size,
+                                                    bc2_sqrt), _p(dst2), Ko, ldd, _stream()), "ga_diloco_outer_adam")
+
+
+def diloco_outer_adam_masked(reps, bits, master, exp_avg, exp_avg_sq, n, sparse_divisor, divisor, *, lerp_w, beta2,
+                             one_m_beta2, eps, wd_factor, l2_wd, step_size, bc2_sqrt):
+    """diloco_outer_masked with the Adam update (ga_diloco_outer_adam_masked), in place
+    over every row of reps: bit-identical to sparta_average_local(reps, n,
+    sparse_divisor, mask=bits) then diloco_outer_adam(reps, ..., dst=reps)."""
+    r2 = _as2d(reps)
+    _gpu(r2, bits, master, exp_avg, exp_avg_sq)
+    K, ld = _rows_ld(r2)
+    _adam_state("diloco_outer_adam_masked", n, master, exp_avg, exp_avg_sq)
+    if r2.shape[1] < n:
+        raise ValueError("diloco_outer_adam_masked: buffers shorter than n")
+    if bits.dtype != torch.int64 or bits.numel() < sparta_mask_words(n) or not bits.is_contiguous():
+        raise ValueError("diloco_outer_adam_masked: bits must be a contiguous int64 tensor of >= ceil(n/64) words")
+    check(lib().ga_diloco_outer_adam_masked(_dtype_code(r2), _p(r2), K, ld, int(n), _p(bits), float(sparse_divisor),
+                                            float(divisor), _p(master), _p(exp_avg), _p(exp_avg_sq),
+                                            *_adam_scalars(lerp_w, beta2, one_m_beta2, eps, wd_factor, l2_wd,
+                                                           step_size, bc2_sqrt), _p(r2), K, ld, _stream()),
+          "ga_diloco_outer_adam_masked")
+
+
 def sparta_gap_table(p):
     """The 64-entry gap table of the Philox mask stream (include/gym_amd.h)."""
     import ctypes

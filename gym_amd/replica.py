@@ -44,7 +44,7 @@ from .comm import Collective
 from .engine import DiLoCoOuter, MeanReduce, Sparta, demo_codec
 from .fused_optim import FUSED, build_fused
 from .strategy.demo import DeMoStrategy
-from .strategy.diloco import DiLoCoStrategy, fused_sgd_hparams
+from .strategy.diloco import DiLoCoStrategy, build_outer_engine
 from .strategy.federated_averaging import FedAvgStrategy
 from .strategy.sparta import MaskDraw, RandomIndexSelector, SPARTAStrategy, draw_masks
 from .strategy.sparta_diloco import SPARTADiLoCoStrategy
@@ -100,7 +100,7 @@ class ReplicaRunner:
         if isinstance(strategy, FedAvgStrategy):
             return True
         if isinstance(strategy, DiLoCoStrategy):
-            return True  # any outer OptimSpec: fused kernel for SGD, torch's optimizer on a master otherwise
+            return True  # any outer OptimSpec: fused kernel for SGD / Adam / AdamW, torch's optimizer otherwise
         return isinstance(strategy, (SimpleReduceStrategy, DeMoStrategy))
 
     def __init__(self, strategy, models, rank, num_nodes):
@@ -149,9 +149,9 @@ class ReplicaRunner:
                           or _PerNodeOptim(spec, models, self.ra.arenas))
             self.max_norm = s.kwargs.get("max_norm") if isinstance(s, DiLoCoStrategy) else s.max_norm
             if isinstance(s, (DiLoCoStrategy, SPARTADiLoCoStrategy)):
-                hp = fused_sgd_hparams(s.outer_optim_spec)
-                if hp is not None:
-                    self.outer = DiLoCoOuter(self.coll, self.K, ld, dev, dt, placement=s.placement_opt, **hp)
+                self.outer = build_outer_engine(s, s.outer_optim_spec, self.coll, self.K, ld, dev, dt)
+                self.outer_optimizer = None
+                if self.outer is not None:
                     self.outer.init_master(self.ra.flat_set[0])
                     # the step may move the replica set itself (every model re-pointed)
                     self.outer.relocate_replicas = self.ra.relocate_params

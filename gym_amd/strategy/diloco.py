@@ -11,15 +11,18 @@ Here, for an SGD-family outer optimizer, it is ONE fused kernel per node
 (ga_diloco_outer: average, pseudo-gradient master - avg, momentum/Nesterov,
 master update, parameter write-back) around one reduce-scatter + one
 all-gather over RCCL; the master copy and momentum are fp32 and sharded over
-the ranks.  Any other outer optimizer class runs torch's optimizer on a GPU
-master copy (replicated on every rank) fed by the same averaging kernel.
+the ranks.  torch's Adam / AdamW as the outer optimizer take the same one pass
+with an Adam update (ga_diloco_outer_adam, master and both moments sharded;
+fused_outer=False keeps torch's optimizer).  Any other outer optimizer class
+runs torch's optimizer on a GPU master copy (replicated on every rank) fed by
+the same averaging kernel.
 """
 from typing import Optional, Union
 
 import torch
 
 from .. import ops
-from ..engine import DiLoCoOuter
+from ..engine import DiLoCoOuter, DiLoCoOuterAdam
 from .communicate_optimize_strategy import CommunicationModule
 from .optim import OptimSpec, ensure_optim_spec
 from .strategy import Strategy, build_inner_optimizer, clip_and_step
@@ -45,6 +48,44 @@ def fused_sgd_hparams(spec: OptimSpec):
     return hp
 
 
+def fused_adam_hparams(spec: OptimSpec):
+    """Hyper-parameters for the fused Adam outer step (DiLoCoOuterAdam) if `spec`
+    is torch's Adam (L2 decay) or AdamW (decoupled decay) with options the kernel
+    covers; None keeps torch's optimizer."""
+    if spec.cls not in (torch.optim.Adam, torch.optim.AdamW):
+        return None
+    # a stand-in kernel layer (tests) written before ga_diloco_outer_adam keeps torch's optimizer
+    if not hasattr(ops, "diloco_outer_adam"):
+        return None
+    kw = dict(spec.kwargs or {})
+    for k in ("foreach", "fused"):
+        kw.pop(k, None)
+    decoupled = spec.cls is torch.optim.AdamW
+    lr = kw.pop("lr", 1e-3)
+    betas = kw.pop("betas", (0.9, 0.999))
+    eps = kw.pop("eps", 1e-8)
+    weight_decay = kw.pop("weight_decay", 1e-2 if decoupled else 0.0)  # torch's AdamW / Adam defaults
+    if kw or isinstance(lr, torch.Tensor):  # amsgrad, maximize, capturable, differentiable, anything unknown
+        return None
+    return dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps),
+                weight_decay=float(weight_decay), decoupled=decoupled)
+
+
+def build_outer_engine(strategy, spec, coll, K_local, n, device, dtype):
+    """The fused outer-step engine of outer OptimSpec `spec`: DiLoCoOuter for plain
+    SGD, DiLoCoOuterAdam for Adam / AdamW unless the strategy was built with
+    fused_outer=False (the A/B switch against torch's optimizer; SGD specs are
+    always fused); None when the spec stays on torch's optimizer."""
+    placement = strategy.placement_opt
+    hp = fused_sgd_hparams(spec)
+    if hp is not None:
+        return DiLoCoOuter(coll, K_local, n, device, dtype, placement=placement, **hp)
+    hp = fused_adam_hparams(spec) if strategy.kwargs.get("fused_outer", True) else None
+    if hp is not None:
+        return DiLoCoOuterAdam(coll, K_local, n, device, dtype, placement=placement, **hp)
+    return None
+
+
 def default_outer_spec():
     return OptimSpec(torch.optim.SGD, lr=0.7, nesterov=True, momentum=0.9)
 
@@ -54,8 +95,8 @@ class DiLoCoCommunicator(CommunicationModule):
     CommunicateOptimizeStrategy (the name sparta_diloco.py:6 imports): every H
     steps (local_step % H == 0 and local_step > 0, diloco.py:62) the outer
     optimizer steps a master copy on master - average and every node takes the
-    master.  The same engines as DiLoCoStrategy: the fused kernel for an
-    SGD-family outer spec, torch's optimizer on an fp32 master otherwise."""
+    master.  The same engines as DiLoCoStrategy: the fused kernel for an SGD,
+    Adam or AdamW outer spec, torch's optimizer on an fp32 master otherwise."""
 
     def __init__(self, H: int = 100, outer_optim: Optional[Union[str, OptimSpec]] = None, **kwargs):
         super().__init__(**kwargs)
@@ -69,9 +110,8 @@ class DiLoCoCommunicator(CommunicationModule):
         arena = s.arena
         # the reference's master copy is rank 0's initial model (diloco.py:81-82)
         s.coll.broadcast_(arena.flat, 0)
-        hp = fused_sgd_hparams(self.outer_optim_spec)
-        if hp is not None:
-            self._engine = DiLoCoOuter(s.coll, 1, arena.n, arena.device, arena.dtype, placement=s.placement_opt, **hp)
+        self._engine = build_outer_engine(s, self.outer_optim_spec, s.coll, 1, arena.n, arena.device, arena.dtype)
+        if self._engine is not None:
             self._engine.init_master(arena.flat)
             s.engine = self._engine  # Strategy.placement_records reads the outer step's record there
         else:
@@ -110,14 +150,12 @@ class DiLoCoStrategy(Strategy):
         arena = self._bind_arena(model)
         # the reference's master copy is rank 0's initial model (diloco.py:81-82)
         self.coll.broadcast_(arena.flat, 0)
-        hp = fused_sgd_hparams(self.outer_optim_spec)
         self.outer_optimizer = None
-        if hp is not None:
-            self.engine = DiLoCoOuter(self.coll, 1, arena.n, arena.device, arena.dtype, placement=self.placement_opt,
-                                      **hp)
+        self.engine = build_outer_engine(self, self.outer_optim_spec, self.coll, 1, arena.n, arena.device,
+                                         arena.dtype)
+        if self.engine is not None:
             self.engine.init_master(arena.flat)
         else:
-            self.engine = None
             self.master = torch.nn.Parameter(arena.flat.detach().float().clone())
             self.outer_optimizer = self.outer_optim_spec.build([self.master])
             self._avg = torch.empty_like(arena.flat)

@@ -231,6 +231,39 @@ GA_API int ga_diloco_outer_masked(int dtype, void* src, int64_t K, int64_t ld_sr
                                   int nesterov, void* dst, int64_t K_out, int64_t ld_dst,
                                   hipStream_t stream);
 
+/*
+ * The outer step with an Adam / AdamW outer optimizer (OptimSpec "adam" / "adamw" as
+ * DiLoCo's outer_optim_spec, diloco.py:26-28), one pass over n elements:
+ *   avg = (sum_{k<K} src_k[i]) / divisor         (fp32, ascending k, true division)
+ *   g   = master[i] - avg
+ *   ga_adam_step's element update of (master[i], g, exp_avg[i], exp_avg_sq[i]) with
+ *   the eight scalars below (torch's _multi_tensor_adam order; see ga_adam_step)
+ *   dst_j[i] = master[i]  for j < K_out
+ * master, exp_avg and exp_avg_sq are fp32 whatever `dtype` (f32 / bf16 src and dst).
+ * There is no first-step flag: zero moments and the bias corrections of step 1
+ * (step_size = -lr / (1 - beta1), bc2_sqrt = sqrt(1 - beta2)) give torch's first
+ * step.  Argument checks as ga_diloco_outer.  Algorithmic bytes (2K + 6) * 4 n for
+ * fp32, in place over K rows.
+ */
+GA_API int ga_diloco_outer_adam(int dtype, const void* src, int64_t K, int64_t ld_src, int64_t n,
+                                float divisor, float* master, float* exp_avg, float* exp_avg_sq,
+                                float lerp_w, float beta2, float one_m_beta2, float eps, float wd_factor,
+                                float l2_wd, float step_size, float bc2_sqrt, void* dst, int64_t K_out,
+                                int64_t ld_dst, hipStream_t stream);
+
+/*
+ * ga_diloco_outer_masked with the Adam update of ga_diloco_outer_adam: SPARTA's
+ * sparse average over the elements selected in `bits` and the outer step, one
+ * pass, bit-identical to ga_sparta_average_local followed by ga_diloco_outer_adam.
+ * In place over all K rows only (dst == src, K_out == K, ld_dst == ld_src).
+ */
+GA_API int ga_diloco_outer_adam_masked(int dtype, void* src, int64_t K, int64_t ld_src, int64_t n,
+                                       const uint64_t* bits, float sparse_divisor, float divisor,
+                                       float* master, float* exp_avg, float* exp_avg_sq, float lerp_w,
+                                       float beta2, float one_m_beta2, float eps, float wd_factor,
+                                       float l2_wd, float step_size, float bc2_sqrt, void* dst,
+                                       int64_t K_out, int64_t ld_dst, hipStream_t stream);
+
 /* ---- SPARTA sparse averaging ------------------------------------------- */
 
 /* Workspace bytes needed by ga_sparta_select for an arena of n elements. */
