@@ -10,8 +10,13 @@ node count is K_total = world * K_local.
   MeanReduce   SimpleReduce grads, FedAvg params     strategy.py:128-142, federated_averaging.py:53-69
   DiLoCoOuter  fused outer SGD/Nesterov step        diloco.py:34-76
   DiLoCoOuterAdam  the same with an Adam/AdamW update  diloco.py:26-28
+  TorchOuter   any other outer optimizer: torch's, on an fp32 master
   Sparta       sparse average (Philox or mask)      sparta.py:24-44
   DeMoCodec    DCT encode/top-k + gather + decode   demo_impl/demo.py:142-209
+
+Shared by them and by their callers in both modes: node_mean (row sum,
+all-reduce, division by K_total) and place_replica_set (the probe-and-move of a
+caller's [K, ld] set that MeanReduce and DiLoCoOuter each guard their own way).
 """
 import math
 
@@ -50,6 +55,38 @@ def default_shard(coll, n, dtype):
     all-reduce."""
     esz = torch.empty((), dtype=dtype).element_size()
     return bool(coll.rccl and coll.exchange and n * esz >= SHARD_MIN_BYTES)
+
+
+def node_mean(coll, reps, out, K_total):
+    """out <- the mean of the rows of `reps` over all K_total nodes: the ascending
+    fp32 sum of the local rows (ga_replica_mean), one all-reduce across the
+    processes, true division by K_total (the reference's `/= num_nodes`)."""
+    ops.replica_mean(reps, out, divisor=1.0)
+    coll.all_reduce_(out)
+    ops.replica_mean(out, out, divisor=float(K_total))
+
+
+def place_replica_set(reps, probe, relocate_replicas, candidates, how):
+    """Up to `candidates` fresh [K, ld] sets timed with `probe(set)` (the step's
+    access pattern, every value written back unchanged) beside `reps` itself;
+    when one beats it the caller's set moves there (relocate_replicas copies the
+    contents and re-points the caller's views).  Returns (the set to use from
+    now on, the buffer that holds it or None, the record)."""
+    from . import placement
+    K, ld = reps.shape
+
+    def as_set(buf):
+        return buf.tensor()[:K * ld].view(K, ld)
+
+    best_buf, times = placement.choose(4 * K * ld, reps.device, lambda b: probe(as_set(b)), probe(reps), candidates,
+                                       PLACEMENT_MAX_FRAC)
+    best = 0
+    if best_buf is not None:
+        best = min(range(len(times)), key=lambda i: times[i])
+        reps = as_set(best_buf)
+        relocate_replicas(reps)
+    return reps, best_buf, {"candidates": len(times), "probe_ms": [round(t, 4) for t in times], "chosen": best,
+                            "how": how}
 
 
 class ShardPlan:
@@ -186,26 +223,13 @@ class MeanReduce:
             return reps
 
         watch = placement.Stopwatch()
-
-        def as_set(buf):
-            return buf.tensor()[:K * ld].view(K, ld)
-
-        def probe(t):
-            return placement.time_probe(lambda: ops.probe_mean_placement(t, self.n))
-
-        best_buf, times = placement.choose(4 * K * ld, reps.device, lambda b: probe(as_set(b)), probe(reps),
-                                           REPLICA_PLACEMENT_CANDIDATES, PLACEMENT_MAX_FRAC)
-        best = 0
-        if best_buf is not None:
-            best = min(range(len(times)), key=lambda i: times[i])
-            new = as_set(best_buf)
-            self.relocate_replicas(new)
-            self._reps_placed = best_buf
-            reps = new
+        reps, buf, self.placement = place_replica_set(
+            reps, lambda t: placement.time_probe(lambda: ops.probe_mean_placement(t, self.n)), self.relocate_replicas,
+            REPLICA_PLACEMENT_CANDIDATES, "the caller's replica set moved to the fastest of fresh [K, ld] allocations; "
+                                          "candidate 0 = where it was")
+        if buf is not None:
+            self._reps_placed = buf
             self._placed_for = (reps.data_ptr(), reps.stride(0))
-        self.placement = {"candidates": len(times), "probe_ms": [round(t, 4) for t in times], "chosen": best,
-                          "how": "the caller's replica set moved to the fastest of fresh [K, ld] allocations; "
-                                 "candidate 0 = where it was"}
         watch.stamp(self.placement)
         return reps
 
@@ -376,26 +400,15 @@ class DiLoCoOuter:
         current master/momentum; the caller's set moves to the fastest one when
         it beats the set's own time (relocate_replicas copies the contents)."""
         from . import placement
-        K, ld = reps.shape
-
-        def as_set(buf):
-            return buf.tensor()[:K * ld].view(K, ld)
-
-        def probe(t):
-            return placement.time_probe(lambda: ops.probe_diloco_placement(t[:, :per], per, self.master, self.mom))
-
-        best_buf, times = placement.choose(4 * K * ld, reps.device, lambda b: probe(as_set(b)), probe(reps),
-                                           REPLICA_PLACEMENT_CANDIDATES, PLACEMENT_MAX_FRAC)
-        best = 0
-        if best_buf is not None:
-            best = min(range(len(times)), key=lambda i: times[i])
-            new = as_set(best_buf)
-            self.relocate_replicas(new)
-            self._reps_placed = best_buf
-            reps = new
-        return reps, {"candidates": len(times), "probe_ms": [round(t, 4) for t in times], "chosen": best,
-                      "how": "the caller's replica set moved to the fastest of fresh [K, ld] allocations "
-                             "(probed against the ordinary master); candidate 0 = where it was"}
+        reps, buf, rec = place_replica_set(
+            reps, lambda t: placement.time_probe(lambda: ops.probe_diloco_placement(t[:, :per], per, self.master,
+                                                                                    self.mom)),
+            self.relocate_replicas, REPLICA_PLACEMENT_CANDIDATES,
+            "the caller's replica set moved to the fastest of fresh [K, ld] allocations "
+            "(probed against the ordinary master); candidate 0 = where it was")
+        if buf is not None:
+            self._reps_placed = buf
+        return reps, rec
 
     def __call__(self, reps, sparse_mask=None):
         """sparse_mask: packed int64 mask words (ops.sparta_pack_mask layout) of a
@@ -483,6 +496,36 @@ class DiLoCoOuterAdam(DiLoCoOuter):
         self.t += 1
 
 
+class TorchOuter:
+    """DiLoCo's outer step for an outer OptimSpec without a fused kernel
+    (diloco.py:26-28, 34-49, 66-74), with DiLoCoOuter's call surface: torch's
+    optimizer on an fp32 master of the node's start (replicated on every
+    process), fed the node average (node_mean); every row takes the master."""
+
+    relocate_replicas = None  # accepted as on DiLoCoOuter; nothing here depends on where the set sits
+
+    def __init__(self, coll: Collective, K_local, n, device, dtype, spec):
+        self.coll, self.spec = coll, spec
+        self.K_total = coll.world * int(K_local)
+        self.avg = torch.empty(n, device=device, dtype=dtype)
+        self.master = self.optimizer = None
+
+    def init_master(self, params_flat):
+        self.master = torch.nn.Parameter(params_flat.detach().float().clone())
+        self.optimizer = self.spec.build([self.master])
+
+    @torch.no_grad()
+    def __call__(self, reps, sparse_mask=None):
+        if sparse_mask is not None:
+            raise ValueError("TorchOuter: no one-pass masked outer step; run Sparta and the outer step one after "
+                             "the other")
+        node_mean(self.coll, reps, self.avg, self.K_total)
+        self.optimizer.zero_grad()
+        self.master.grad = self.master.detach() - self.avg.float()
+        self.optimizer.step()
+        reps.copy_(self.master.detach())  # broadcast over the rows
+
+
 def sparta_capacity(n, p):
     """Packed-value capacity for a Philox draw of n elements at rate p: mean +
     16 sigma + 1024 (overflow is flagged on the device and raised by check())."""
@@ -519,6 +562,12 @@ class Sparta:
             self.cap = cap
             self.idx = torch.empty(cap, dtype=torch.int32, device=self.device)
             self.vals = torch.empty(cap, dtype=self.dtype, device=self.device)
+
+    @staticmethod
+    def pack(mask, bits):
+        """bits <- the uint8 mask arena `mask` as one bit per element (ga_sparta_pack_mask)."""
+        ops.sparta_pack_mask(mask, mask.numel(), bits)
+        return bits
 
     def check(self):
         """Raise if an earlier Philox step selected more than the capacity.

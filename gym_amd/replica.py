@@ -14,12 +14,19 @@ the dataset factory called with the node's rank), gradient accumulation over
 batch_size // minibatch_size minibatches with `grad /= batch_size /
 minibatch_size`, its own clip_grad_norm_, then the strategy step.  Supported
 strategies: SimpleReduce, DiLoCo (any outer optimizer: the fused kernel for
-SGD-family, torch's optimizer on an fp32 master otherwise), SPARTA (every
+SGD, Adam and AdamW, torch's optimizer on an fp32 master otherwise), SPARTA (every
 selector: the torch-drawn masks of node 0 -- the reference uses rank 0's --
 or the Philox stream), FedAvg (full or island averaging), DeMo, SPARTA+DiLoCo (SPARTA's
 average and DiLoCo's outer step as above; in one process a step where both fire is
 one pass, ga_diloco_outer_masked).  Anything else runs on the process-per-node path
 (ReplicaRunner.supports).
+
+The step parts are the process-per-node strategies' own, built here with
+K_local = K: the outer step of strategy.diloco.build_outer_engine, SPARTA's
+per-step part strategy.sparta.SparseAverage (fed node 0's parameter list),
+strategy.strategy.clip_and_step per node for a non-fusable inner optimizer,
+engine.node_mean.  What this module adds is the [K, ld] set they run over, the
+choice of the one-pass boundary step and FedAvg's islands over a row table.
 
 The K nodes' forward/backward passes run one node after the other by default
 (replica_forward="loop": each node's gradients bit-identical to its own
@@ -41,14 +48,14 @@ from torch.utils.data import DataLoader
 from . import ops
 from .arena import ReplicaArena
 from .comm import Collective
-from .engine import DiLoCoOuter, MeanReduce, Sparta, demo_codec
-from .fused_optim import FUSED, build_fused
+from .engine import DiLoCoOuter, MeanReduce, demo_codec, node_mean
+from .fused_optim import build_fused
 from .strategy.demo import DeMoStrategy
 from .strategy.diloco import DiLoCoStrategy, build_outer_engine
 from .strategy.federated_averaging import FedAvgStrategy
-from .strategy.sparta import MaskDraw, RandomIndexSelector, SPARTAStrategy, draw_masks
+from .strategy.sparta import SparseAverage, SPARTAStrategy
 from .strategy.sparta_diloco import SPARTADiLoCoStrategy
-from .strategy.strategy import SimpleReduceStrategy, clip_arena_grad_norm_
+from .strategy.strategy import SimpleReduceStrategy, clip_and_step
 
 
 def consecutive_runs(xs):
@@ -84,10 +91,7 @@ class _PerNodeOptim:
 
     def step(self, max_norm=None):
         for a, o in zip(self.arenas, self.opts):
-            if max_norm:
-                a.sync_grads()
-                clip_arena_grad_norm_(a.grad_flat, max_norm)
-            o.step()
+            clip_and_step(o, a, max_norm)
 
 
 class ReplicaRunner:
@@ -147,21 +151,16 @@ class ReplicaRunner:
             # one fused launch over all K nodes (ArenaAdam / ArenaSGD), or K torch optimizers
             self.optim = (build_fused(spec, self.ra.params, self.ra, s.placement_opt)
                           or _PerNodeOptim(spec, models, self.ra.arenas))
-            self.max_norm = s.kwargs.get("max_norm") if isinstance(s, DiLoCoStrategy) else s.max_norm
+            # a falsy max_norm: no clipping, on the fused and the per-node optimizers alike
+            self.max_norm = (s.kwargs.get("max_norm") if isinstance(s, DiLoCoStrategy) else s.max_norm) or None
             if isinstance(s, (DiLoCoStrategy, SPARTADiLoCoStrategy)):
+                # the fused kernel, or torch's optimizer on an fp32 master of node 0's start
+                # (diloco.py:26-28, 81-89) for any other outer OptimSpec
                 self.outer = build_outer_engine(s, s.outer_optim_spec, self.coll, self.K, ld, dev, dt)
-                self.outer_optimizer = None
-                if self.outer is not None:
-                    self.outer.init_master(self.ra.flat_set[0])
-                    # the step may move the replica set itself (every model re-pointed)
-                    self.outer.relocate_replicas = self.ra.relocate_params
-                else:
-                    # any other outer OptimSpec (diloco.py:26-28): torch's optimizer on an fp32
-                    # master of node 0's start (diloco.py:81-89), fed the node average
-                    self.outer = self._generic_outer
-                    self.master = torch.nn.Parameter(self.ra.flat_set[0].detach().float().clone())
-                    self.outer_optimizer = s.outer_optim_spec.build([self.master])
-                    self._avg = torch.empty(ld, device=dev, dtype=dt)
+                self.outer.init_master(self.ra.flat_set[0])
+                self.outer_optimizer = getattr(self.outer, "optimizer", None)
+                # the step may move the replica set itself (every model re-pointed)
+                self.outer.relocate_replicas = self.ra.relocate_params
             self.islands = (isinstance(s, FedAvgStrategy) and s.island_size is not None
                             and s.island_size < num_nodes)
             if isinstance(s, (SimpleReduceStrategy, FedAvgStrategy)) and not self.islands:
@@ -174,22 +173,13 @@ class ReplicaRunner:
                 self._isl_row = torch.empty(1, ld, device=dev, dtype=dt)
                 self._isl_all = None  # [num_nodes, ld]: every node's parameters, gathered (processes > 1)
             elif isinstance(s, (SPARTAStrategy, SPARTADiLoCoStrategy)):
-                self.sparta = Sparta(self.coll, self.K, ld, dev, dt, s.index_selector.p)
-                sel = s.index_selector
-                self.philox = isinstance(sel, RandomIndexSelector) and sel.mask_source == "philox"
-                if self.philox:
-                    t = torch.tensor([torch.initial_seed() & (2**63 - 1)], dtype=torch.int64, device=dev)
-                    self.coll.broadcast_(t, 0)
-                    self.seed = int(t.item())
-                else:
-                    self.mask = torch.zeros(ld, dtype=torch.uint8, device=dev)
-                    self.bits = torch.zeros(ops.sparta_mask_words(ld), dtype=torch.int64, device=dev)
-                    self.draw = MaskDraw()
-                self.iteration = 0
+                # node 0's selector masks and grad-less tensors (the reference uses rank 0's)
+                self.sparta = SparseAverage()
+                self.sparta.bind(s.index_selector, self.coll, self.K, self.ra.layout, ld, dev, dt)
             if isinstance(s, SPARTADiLoCoStrategy):
                 # a boundary step as one pass: needs the mask as packed words in memory, every node in
                 # this process, and the fused outer engine
-                self.fuse = bool(s.fuse_boundary and not self.philox and not self.coll.exchange
+                self.fuse = bool(s.fuse_boundary and not self.sparta.philox and not self.coll.exchange
                                  and isinstance(self.outer, DiLoCoOuter))
                 s.fuse_boundary = self.fuse
                 if isinstance(self.outer, DiLoCoOuter):
@@ -220,28 +210,28 @@ class ReplicaRunner:
         elif isinstance(s, SimpleReduceStrategy):
             self.ra.sync_grads()
             self.mean(G)
-            self._inner()
+            self.optim.step(max_norm=self.max_norm)
         elif isinstance(s, DiLoCoStrategy):
-            self._inner()
+            self.optim.step(max_norm=self.max_norm)
             if s.local_step % s.H == 0 and s.local_step > 0:
                 self.outer(P)
         elif isinstance(s, SPARTAStrategy):
-            self._inner()
-            self._sparse_average(P)
-            self.iteration += 1
+            self.optim.step(max_norm=self.max_norm)
+            self.sparta(P, self.ra.arenas[0].params, defer=True)
+            self.sparta.iteration += 1
         elif isinstance(s, SPARTADiLoCoStrategy):
-            self._inner()
+            self.optim.step(max_norm=self.max_norm)
             boundary = s.local_step % s.H == 0 and s.local_step > 0
             if boundary and self.fuse:
-                self.outer(P, sparse_mask=self._boundary_bits())
+                self.outer(P, sparse_mask=self.sparta.boundary_bits(self.ra.arenas[0].params))
             else:
-                self._sparse_average(P)
+                self.sparta(P, self.ra.arenas[0].params, defer=True)
                 if boundary:
                     self.outer(P)
-            s.mask_draw = "philox" if self.philox else self.draw.mode
-            self.iteration += 1
+            s.mask_draw = self.sparta.mask_draw
+            self.sparta.iteration += 1
         elif isinstance(s, FedAvgStrategy):
-            self._inner()
+            self.optim.step(max_norm=self.max_norm)
             if s.local_step % s.H == 0 and s.local_step > 0:
                 if self.islands:
                     self._island_average(P)
@@ -279,21 +269,6 @@ class ReplicaRunner:
         self.delta = tens[2]
         self._placed = bufs  # own the memory the sets now live in
 
-    def _generic_outer(self, P):
-        """DiLoCo's outer step for a non-SGD outer optimizer (diloco.py:34-49,
-        66-74) over the K local nodes: the ascending fp32 sum of the rows
-        (ga_replica_mean), an all-reduce across processes, true division by
-        num_nodes (the reference's `/= num_nodes`), master.grad = master - avg,
-        the torch optimizer's step, and the master written to every row -- the
-        arithmetic of DiLoCoStrategy._outer_step on each process-per-node rank."""
-        ops.replica_mean(P, self._avg, divisor=1.0)
-        self.coll.all_reduce_(self._avg)
-        ops.replica_mean(self._avg, self._avg, divisor=float(self.num_nodes))
-        self.outer_optimizer.zero_grad()
-        self.master.grad = self.master.detach() - self._avg.float()
-        self.outer_optimizer.step()
-        P.copy_(self.master.detach().to(P.dtype).unsqueeze(0).expand_as(P))
-
     def _island_average(self, P):
         """FedAvg islands (federated_averaging.py:26-69) over the nodes of this
         process: the first process shuffles the node ids with Python's `random`
@@ -330,65 +305,10 @@ class ReplicaRunner:
             for a0, a1 in consecutive_runs(mine):
                 ops.replica_mean(self._isl_row, P[a0 - lo:a1 - lo + 1], divisor=1.0)
 
-    def _grad_less(self):
-        """Indices of node 0's tensors without a gradient (skipped, sparta.py:29-30)."""
-        a0 = self.ra.arenas[0]
-        return [i for i, p in enumerate(a0.params) if not p.requires_grad or p.grad is None]
-
-    def _skip_table(self):
-        L = self.ra.layout
-        rng = []
-        for i in self._grad_less():
-            lo, hi = L.offsets[i], L.offsets[i] + L.numels[i]
-            if rng and rng[-1][1] == lo:
-                rng[-1][1] = hi
-            else:
-                rng.append([lo, hi])
-        return torch.tensor(rng, dtype=torch.int64, device=self.ra.device).view(-1, 2) if rng else None
-
-    def _build_mask(self):
-        """Node 0's selector masks (the reference broadcasts rank 0's,
-        sparta.py:32-37) as one uint8 arena; the engine packs the first
-        process's and broadcasts it to the others."""
-        a0 = self.ra.arenas[0]
-        packed = draw_masks(self.s.index_selector, a0.params, self.ra.layout.views(self.mask), set(self._grad_less()),
-                            self.iteration, self.draw, bits=self.bits, coll=self.coll, defer=True)
-        self.mask_shared = packed is not None
-        return self.mask if packed is None else packed
-
-    def _sparse_average(self, P):
-        s = self.s
-        if self.philox:
-            self.sparta(P, seed=self.seed, iteration=self.iteration, skip=self._skip_table())
-        else:
-            sel = s.index_selector
-            m = self._build_mask()
-            self.sparta(P, mask=m, mask_cap=self.sparta.cap if type(sel) is RandomIndexSelector else None,
-                        mask_shared=self.mask_shared)
-
-    def _boundary_bits(self):
-        """This step's mask as packed words for the one-pass boundary step: the
-        draw of _build_mask made now instead of inside the SPARTA kernel (the same
-        bits, the generator advanced the same way), or the byte arena packed."""
-        a0 = self.ra.arenas[0]
-        packed = draw_masks(self.s.index_selector, a0.params, self.ra.layout.views(self.mask), set(self._grad_less()),
-                            self.iteration, self.draw, bits=self.bits, coll=self.coll, defer=False)
-        if packed is None:
-            ops.sparta_pack_mask(self.mask, self.mask.numel(), self.bits)
-        return self.bits
-
-    def _inner(self):
-        if isinstance(self.optim, FUSED):
-            self.optim.step(max_norm=self.max_norm or None)
-        else:
-            self.optim.step(max_norm=self.max_norm)
-
     def averaged_flat(self):
         """The mean over all num_nodes nodes' parameters (a new [ld] buffer)."""
         avg = torch.empty(self.ra.ld, device=self.ra.device, dtype=self.ra.dtype)
-        ops.replica_mean(self.ra.flat_set, avg, divisor=1.0)
-        self.coll.all_reduce_(avg)
-        ops.replica_mean(avg, avg, divisor=float(self.num_nodes))
+        node_mean(self.coll, self.ra.flat_set, avg, self.num_nodes)
         return avg
 
 

@@ -42,7 +42,7 @@ class CommunicateOptimizeStrategy(Strategy):
             m.strategy = self
 
     def step(self):
-        clip_and_step(self, self.max_norm)
+        clip_and_step(self.optim, self.arena, self.max_norm)
         self._communicate()
         super().step()
 

@@ -15,14 +15,16 @@ the ranks.  torch's Adam / AdamW as the outer optimizer take the same one pass
 with an Adam update (ga_diloco_outer_adam, master and both moments sharded;
 fused_outer=False keeps torch's optimizer).  Any other outer optimizer class
 runs torch's optimizer on a GPU master copy (replicated on every rank) fed by
-the same averaging kernel.
+the same averaging kernel (engine.TorchOuter).  build_outer_engine picks among
+the three for both modes -- one node per process here, K nodes per process in
+gym_amd.replica -- so neither holds outer-step arithmetic of its own.
 """
 from typing import Optional, Union
 
 import torch
 
 from .. import ops
-from ..engine import DiLoCoOuter, DiLoCoOuterAdam
+from ..engine import DiLoCoOuter, DiLoCoOuterAdam, TorchOuter
 from .communicate_optimize_strategy import CommunicationModule
 from .optim import OptimSpec, ensure_optim_spec
 from .strategy import Strategy, build_inner_optimizer, clip_and_step
@@ -72,10 +74,11 @@ def fused_adam_hparams(spec: OptimSpec):
 
 
 def build_outer_engine(strategy, spec, coll, K_local, n, device, dtype):
-    """The fused outer-step engine of outer OptimSpec `spec`: DiLoCoOuter for plain
-    SGD, DiLoCoOuterAdam for Adam / AdamW unless the strategy was built with
-    fused_outer=False (the A/B switch against torch's optimizer; SGD specs are
-    always fused); None when the spec stays on torch's optimizer."""
+    """The outer step of outer OptimSpec `spec` over a [K_local, n] set:
+    DiLoCoOuter for plain SGD, DiLoCoOuterAdam for Adam / AdamW unless the
+    strategy was built with fused_outer=False (the A/B switch against torch's
+    optimizer; SGD specs are always fused), TorchOuter (torch's optimizer on an
+    fp32 master) for every other spec."""
     placement = strategy.placement_opt
     hp = fused_sgd_hparams(spec)
     if hp is not None:
@@ -83,7 +86,22 @@ def build_outer_engine(strategy, spec, coll, K_local, n, device, dtype):
     hp = fused_adam_hparams(spec) if strategy.kwargs.get("fused_outer", True) else None
     if hp is not None:
         return DiLoCoOuterAdam(coll, K_local, n, device, dtype, placement=placement, **hp)
-    return None
+    return TorchOuter(coll, K_local, n, device, dtype, spec)
+
+
+def start_outer(holder, strategy, spec, arena):
+    """One node's outer step (process mode), its master a copy of `arena`, and
+    the names tests and Strategy.placement_records read: the fused engine as
+    strategy.engine; torch's optimizer and the Parameter its state is keyed by
+    as holder.outer_optimizer / holder.master (None / unset when fused)."""
+    outer = build_outer_engine(strategy, spec, strategy.coll, 1, arena.n, arena.device, arena.dtype)
+    outer.init_master(arena.flat)
+    holder.outer_optimizer = None
+    if isinstance(outer, TorchOuter):
+        holder.outer_optimizer, holder.master = outer.optimizer, outer.master
+    else:
+        strategy.engine = outer
+    return outer
 
 
 def default_outer_spec():
@@ -95,46 +113,24 @@ class DiLoCoCommunicator(CommunicationModule):
     CommunicateOptimizeStrategy (the name sparta_diloco.py:6 imports): every H
     steps (local_step % H == 0 and local_step > 0, diloco.py:62) the outer
     optimizer steps a master copy on master - average and every node takes the
-    master.  The same engines as DiLoCoStrategy: the fused kernel for an SGD,
-    Adam or AdamW outer spec, torch's optimizer on an fp32 master otherwise."""
+    master.  The same outer step as DiLoCoStrategy (build_outer_engine)."""
 
     def __init__(self, H: int = 100, outer_optim: Optional[Union[str, OptimSpec]] = None, **kwargs):
         super().__init__(**kwargs)
         self.H = H
         self.outer_optim_spec = ensure_optim_spec(outer_optim, default_outer_spec())
-        self._engine = None
         self.outer_optimizer = None
 
     def _init_node(self, model, rank, num_nodes):
         s = self.strategy
-        arena = s.arena
         # the reference's master copy is rank 0's initial model (diloco.py:81-82)
-        s.coll.broadcast_(arena.flat, 0)
-        self._engine = build_outer_engine(s, self.outer_optim_spec, s.coll, 1, arena.n, arena.device, arena.dtype)
-        if self._engine is not None:
-            self._engine.init_master(arena.flat)
-            s.engine = self._engine  # Strategy.placement_records reads the outer step's record there
-        else:
-            self.master = torch.nn.Parameter(arena.flat.detach().float().clone())
-            self.outer_optimizer = self.outer_optim_spec.build([self.master])
-            self._avg = torch.empty_like(arena.flat)
+        s.coll.broadcast_(s.arena.flat, 0)
+        self._outer = start_outer(self, s, self.outer_optim_spec, s.arena)
 
     def communicate(self, model, rank: int, num_nodes: int, local_step: int) -> None:
-        if not (local_step % self.H == 0 and local_step > 0):
-            return
-        s = self.strategy
-        s.arena.check_bound()
-        if self._engine is not None:
-            self._engine(s.arena.flat.view(1, -1))
-            return
-        self._avg.copy_(s.arena.flat)
-        s.coll.all_reduce_(self._avg)
-        ops.replica_mean(self._avg, self._avg, divisor=s.coll.world)
-        self.outer_optimizer.zero_grad()
-        self.master.grad = self.master.detach() - self._avg.float()
-        self.outer_optimizer.step()
-        with torch.no_grad():
-            s.arena.flat.copy_(self.master)
+        if local_step % self.H == 0 and local_step > 0:
+            self.strategy.arena.check_bound()
+            self._outer(self.strategy.arena.flat.view(1, -1))
 
 
 class DiLoCoStrategy(Strategy):
@@ -150,34 +146,28 @@ class DiLoCoStrategy(Strategy):
         arena = self._bind_arena(model)
         # the reference's master copy is rank 0's initial model (diloco.py:81-82)
         self.coll.broadcast_(arena.flat, 0)
-        self.outer_optimizer = None
-        self.engine = build_outer_engine(self, self.outer_optim_spec, self.coll, 1, arena.n, arena.device,
-                                         arena.dtype)
-        if self.engine is not None:
-            self.engine.init_master(arena.flat)
-        else:
-            self.master = torch.nn.Parameter(arena.flat.detach().float().clone())
-            self.outer_optimizer = self.outer_optim_spec.build([self.master])
-            self._avg = torch.empty_like(arena.flat)
+        self.outer = start_outer(self, self, self.outer_optim_spec, arena)
         self.optim = build_inner_optimizer(self.inner_optim_spec, model, arena, self.placement_opt)
         self._setup_scheduler()
 
+    @property
+    def engine(self):
+        """The fused engine (Strategy.placement_records reads its record), None
+        while the outer step is torch's optimizer.  Assigning an engine replaces
+        the outer step, as it did when this was the only place it lived."""
+        outer = getattr(self, "outer", None)
+        return None if isinstance(outer, TorchOuter) else outer
+
+    @engine.setter
+    def engine(self, engine):
+        self.outer = engine
+
     def _outer_step(self):
         self.arena.check_bound()
-        if self.engine is not None:
-            self.engine(self.arena.flat.view(1, -1))
-            return
-        self._avg.copy_(self.arena.flat)
-        self.coll.all_reduce_(self._avg)
-        ops.replica_mean(self._avg, self._avg, divisor=self.coll.world)
-        self.outer_optimizer.zero_grad()
-        self.master.grad = self.master.detach() - self._avg.float()
-        self.outer_optimizer.step()
-        with torch.no_grad():
-            self.arena.flat.copy_(self.master)
+        self.outer(self.arena.flat.view(1, -1))
 
     def step(self):
-        clip_and_step(self, self.kwargs.get("max_norm"))  # diloco.py:52-59
+        clip_and_step(self.optim, self.arena, self.kwargs.get("max_norm"))  # diloco.py:52-59
         if self.local_step % self.H == 0 and self.local_step > 0:
             self._outer_step()
         super().step()

@@ -31,6 +31,11 @@ mask_source=...)):
       table passed to the kernel).
 The ShuffledSequential / Partitioned selectors are the reference's algorithms
 (the same torch draws on the device) feeding the mask-mode kernels.
+
+SparseAverage is the one copy of the per-step orchestration (shared seed, skip
+table, mask arena and draw state, the mask_cap rule, the iteration counter):
+SparseCommunicator runs it over its node's arena as a [1, n] set, the batched
+replica loop (gym_amd.replica) over its [K, ld] set with node 0's parameters.
 """
 import math
 import warnings
@@ -341,101 +346,124 @@ class PartitionedIndexSelector(IndexSelector):
         return mask
 
 
-class SparseCommunicator(CommunicationModule):
-    def __init__(self, index_selector, **kwargs):
-        super().__init__(**kwargs)
-        self.index_selector = index_selector
+class SparseAverage:
+    """SPARTA's per-step orchestration around the Sparta engine, over the
+    [K_local, ld] set of one process: one simulated node per process
+    (SparseCommunicator, K_local = 1) or K of them (gym_amd.replica).  Holds
+    the iteration counter (the caller advances it once per training step) and,
+    from bind() on, the selector, the engine and per mask source the run's
+    Philox seed or the mask arena, its packed words and the draw state."""
+
+    def __init__(self):
         self.iteration = 0
-        self._engine = None
-        self._seed = None
-        self._mask = None
-        self._skip_key = None
-        self._skip = None
-        self._draw = MaskDraw()
-        self.mask_draw = None  # "philox" | "fused" | "torch" once a step has drawn (read by __config__)
+        self.selector = self.engine = None
+        self.draw = MaskDraw()
 
-    def _init_node(self, model, rank, num_nodes):
-        pass
+    @property
+    def philox(self):
+        return isinstance(self.selector, RandomIndexSelector) and self.selector.mask_source == "philox"
 
-    def _setup(self):
-        s = self.strategy
-        a = s.arena
-        self._engine = Sparta(s.coll, 1, a.n, a.device, a.dtype, self.index_selector.p)
+    @property
+    def mask_draw(self):
+        """Which mask draw the last step ran: "philox" | "fused" | "torch"."""
+        return "philox" if self.philox else self.draw.mode
 
-    def _philox_mode(self):
-        sel = self.index_selector
-        return isinstance(sel, RandomIndexSelector) and sel.mask_source == "philox"
+    def bind(self, selector, coll, K_local, layout, n, device, dtype):
+        """The engine over [K_local, n] sets of arena `layout`; Philox: rank 0's
+        torch.initial_seed(), broadcast once; else the uint8 mask arena and its
+        packed int64 words."""
+        self.selector, self.coll, self.layout = selector, coll, layout
+        self.engine = Sparta(coll, K_local, n, device, dtype, self.selector.p)
+        if self.philox:
+            t = torch.tensor([torch.initial_seed() & (2**63 - 1)], dtype=torch.int64, device=device)
+            coll.broadcast_(t, 0)
+            self.seed = int(t.item())
+            self._skip_key = self._skip = None
+        else:
+            self.mask = torch.zeros(n, dtype=torch.uint8, device=device)
+            self.bits = torch.zeros(ops.sparta_mask_words(n), dtype=torch.int64, device=device)
 
-    def _shared_seed(self):
-        if self._seed is None:
-            s = self.strategy
-            t = torch.tensor([torch.initial_seed() & (2**63 - 1)], dtype=torch.int64, device=s.arena.device)
-            s.coll.broadcast_(t, 0)
-            self._seed = int(t.item())
-        return self._seed
+    def check(self):
+        if self.engine is not None:
+            self.engine.check()
 
-    def _skip_table(self):
-        """[lo, hi) arena ranges of the tensors that are skipped this step
-        (`not requires_grad or grad is None`, sparta.py:29-30), merged; None
-        when every tensor takes part.  Cached on the device while unchanged."""
-        a = self.strategy.arena
-        key = tuple(i for i, p in enumerate(a.params) if not p.requires_grad or p.grad is None)
+    @staticmethod
+    def _skipped(params):
+        """Indices of the tensors skipped this step (`not requires_grad or grad
+        is None`, sparta.py:29-30), read from the leading node's parameters."""
+        return tuple(i for i, p in enumerate(params) if not p.requires_grad or p.grad is None)
+
+    def _skip_table(self, key):
+        """The skipped tensors' [lo, hi) arena ranges, merged; None when every
+        tensor takes part.  Cached on the device while the set is unchanged."""
         if key != self._skip_key:
-            rng = []
+            L, rng = self.layout, []
             for i in key:
-                lo, hi = a.layout.offsets[i], a.layout.offsets[i] + a.layout.numels[i]
+                lo, hi = L.offsets[i], L.offsets[i] + L.numels[i]
                 if rng and rng[-1][1] == lo:
                     rng[-1][1] = hi
                 else:
                     rng.append([lo, hi])
-            self._skip = torch.tensor(rng, dtype=torch.int64, device=a.device).view(-1, 2) if rng else None
+            self._skip = torch.tensor(rng, dtype=torch.int64, device=self.engine.device).view(-1, 2) if rng else None
             self._skip_key = key
         return self._skip
 
-    def _build_mask(self, model):
-        """Reference mask path: per-tensor selector draws into one uint8 mask
-        arena (frozen / grad-less tensors stay 0); the engine packs rank 0's
-        and broadcasts it."""
-        s = self.strategy
-        a = s.arena
-        if self._mask is None:
-            self._mask = torch.zeros(a.n, dtype=torch.uint8, device=a.device)
-            self._bits = torch.zeros(ops.sparta_mask_words(a.n), dtype=torch.int64, device=a.device)
-        skip = {i for i, p in enumerate(a.params) if not p.requires_grad or p.grad is None}
-        packed = draw_masks(self.index_selector, a.params, a.layout.views(self._mask), skip, self.iteration,
-                            self._draw, bits=self._bits, coll=s.coll)
-        self._shared = packed is not None
-        return self._mask if packed is None else packed
+    def _draw(self, params, defer):
+        """The selector's masks of the leading node (the reference broadcasts
+        rank 0's, sparta.py:32-37) into the uint8 arena, skipped tensors 0, or
+        what draw_masks hands back instead: the packed words, or with `defer`
+        the draw for the SPARTA kernel to make."""
+        return draw_masks(self.selector, params, self.layout.views(self.mask), set(self._skipped(params)),
+                          self.iteration, self.draw, bits=self.bits, coll=self.coll, defer=defer)
 
-    def _mask_cap(self):
-        """Selected-count bound for Bernoulli masks (no host sync per step);
-        None (exact count read back) for the deterministic-cycle and custom
-        selectors."""
-        if type(self.index_selector) is RandomIndexSelector:
-            return self._engine.cap
-        return None
+    def __call__(self, reps, params, defer=False):
+        """This step's sparse average over `reps`; `params`: the leading node's
+        parameter list.  defer: the fused reference draw may run inside the
+        SPARTA kernel (draw_masks)."""
+        if self.philox:
+            self.engine(reps, seed=self.seed, iteration=self.iteration, skip=self._skip_table(self._skipped(params)))
+            return
+        packed = self._draw(params, defer)
+        # selected-count bound for Bernoulli masks (no host sync per step); None (exact count read
+        # back) for the deterministic-cycle and custom selectors
+        cap = self.engine.cap if type(self.selector) is RandomIndexSelector else None
+        self.engine(reps, mask=self.mask if packed is None else packed, mask_cap=cap, mask_shared=packed is not None)
+
+    def boundary_bits(self, params):
+        """This step's mask as packed words for the one-pass boundary step: the
+        draw of __call__ made now instead of inside the SPARTA kernel (the same
+        bits, the generator advanced the same way), or the byte arena packed."""
+        return self.bits if self._draw(params, False) is not None else self.engine.pack(self.mask, self.bits)
+
+
+class SparseCommunicator(CommunicationModule):
+    def __init__(self, index_selector, **kwargs):
+        super().__init__(**kwargs)
+        self.index_selector = index_selector
+        self._sparse = SparseAverage()  # bound at the first exchange, to the selector set by then
+        self.mask_draw = None  # "philox" | "fused" | "torch" once a step has drawn (read by __config__)
+
+    iteration = property(lambda self: self._sparse.iteration)
+    _seed = property(lambda self: self._sparse.seed)  # the run's Philox seed, once an exchange has drawn it
+
+    def _init_node(self, model, rank, num_nodes):
+        pass
 
     def finish(self):
-        if self._engine is not None:
-            self._engine.check()
+        self._sparse.check()
 
     def communicate(self, model, rank: int, num_nodes: int, local_step: int) -> None:
+        sp = self._sparse
         if num_nodes > 1:
-            if self._engine is None:
-                self._setup()
             s = self.strategy
-            s.arena.check_bound()
+            a = s.arena
+            if sp.engine is None:
+                sp.bind(self.index_selector, s.coll, 1, a.layout, a.n, a.device, a.dtype)
+            a.check_bound()
             with torch.no_grad():
-                reps = s.arena.flat.view(1, -1)
-                if self._philox_mode():
-                    self._engine(reps, seed=self._shared_seed(), iteration=self.iteration, skip=self._skip_table())
-                    self.mask_draw = "philox"
-                else:
-                    m = self._build_mask(model)
-                    self._engine(reps, mask=m, mask_cap=self._mask_cap(), mask_shared=self._shared)
-                    self.mask_draw = self._draw.mode
-                s.mask_draw = self.mask_draw
-        self.iteration += 1
+                sp(a.flat.view(1, -1), a.params)
+            self.mask_draw = s.mask_draw = sp.mask_draw
+        sp.iteration += 1
 
 
 class SPARTAStrategy(CommunicateOptimizeStrategy):

@@ -47,17 +47,18 @@ def build_inner_optimizer(spec, model, arena, placement=True):
     return build_fused(spec, model.parameters(), arena, placement) or spec.build(model)
 
 
-def clip_and_step(strategy, max_norm):
-    """clip_grad_norm_(max_norm) (if set) then the inner optimizer step; fused
-    into the ArenaAdam / ArenaSGD step (norm reduction + device-side coefficient)."""
+def clip_and_step(optim, arena, max_norm):
+    """clip_grad_norm_(max_norm) (if set) over one node's `arena`, then its inner
+    optimizer's step; fused into the ArenaAdam / ArenaSGD step (norm reduction +
+    device-side coefficient)."""
     from ..fused_optim import FUSED
-    if isinstance(strategy.optim, FUSED):
-        strategy.optim.step(max_norm=max_norm or None)
+    if isinstance(optim, FUSED):
+        optim.step(max_norm=max_norm or None)
         return
     if max_norm:
-        strategy.arena.sync_grads()
-        clip_arena_grad_norm_(strategy.arena.grad_flat, max_norm)
-    strategy.optim.step()
+        arena.sync_grads()
+        clip_arena_grad_norm_(arena.grad_flat, max_norm)
+    optim.step()
 
 
 def clip_arena_grad_norm_(grad_flat, max_norm):
@@ -163,7 +164,7 @@ class Strategy(ABC, LogModule):
 
     def __config__(self):
         cfg = super().__config__(["iteration", "local_step", "lr_callbacks", "model", "optim", "scheduler",
-                                  "arena", "coll", "engine"])
+                                  "arena", "coll", "engine", "outer"])
         cfg["strategy"] = self.__class__.__name__
         cfg["placement"] = {"enabled": self.placement_opt is not False, "records": self.placement_records()}
         return cfg
@@ -188,5 +189,5 @@ class SimpleReduceStrategy(Strategy):
     def step(self):
         self.arena.sync_grads()
         self.engine(self.arena.grad_flat.view(1, -1))
-        clip_and_step(self, self.max_norm)
+        clip_and_step(self.optim, self.arena, self.max_norm)
         super().step()

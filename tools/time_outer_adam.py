@@ -4,10 +4,10 @@ launches between two device events, the first two forms alternated for --pairs
 pairs (the spread of the pairs is the noise):
 
   (a) fused: DiLoCoOuterAdam, one ga_diloco_outer_adam launch, (8K + 24) n bytes;
-  (b) generic: the call sequence the replica runner runs for an outer optimizer
-      without a fused engine (ReplicaRunner._generic_outer): the K-row sum, the
-      divide, master - avg, torch.optim.Adam's step on an fp32 master, the copy of
-      the master to all K rows;
+  (b) generic: the outer step both modes run for an outer optimizer without a
+      fused kernel (engine.TorchOuter): the K-row sum, the divide, master - avg,
+      torch.optim.Adam's step on an fp32 master, the copy of the master to all K
+      rows;
   (c) ga_diloco_outer with momentum on the same rows, (8K + 16) n bytes: the same
       access pattern less one state stream.
 
@@ -28,8 +28,9 @@ sys.path.insert(0, ROOT)
 from gym_amd import ops  # noqa: E402
 from gym_amd.arena import ArenaLayout  # noqa: E402
 from gym_amd.comm import Collective  # noqa: E402
-from gym_amd.engine import DiLoCoOuterAdam  # noqa: E402
+from gym_amd.engine import DiLoCoOuterAdam, TorchOuter  # noqa: E402
 from gym_amd.shapes import MODELS  # noqa: E402
+from gym_amd.strategy.optim import OptimSpec  # noqa: E402
 
 PEAK = 8e12  # B/s, MI355X HBM3E
 SGD = dict(lr=0.7, momentum=0.9, dampening=0.0, weight_decay=0.0, nesterov=True)
@@ -69,32 +70,20 @@ def main():
             reps[k].normal_(std=0.02)
         eng = DiLoCoOuterAdam(coll, K, n, dev, torch.float32, lr=LR, placement=False)
         eng.init_master(reps[0])
-        # (b): the generic path's own buffers and optimizer
-        master = torch.nn.Parameter(reps[0].detach().float().clone())
-        opt = torch.optim.Adam([master], lr=LR)
-        avg = torch.empty(n, device=dev)
+        # (b): the generic outer step, with its own master, optimizer and average buffer
+        generic = TorchOuter(coll, K, n, dev, torch.float32, OptimSpec(torch.optim.Adam, lr=LR))
+        generic.init_master(reps[0])
         # (c)
         sgd_master, sgd_mom = reps[0].clone(), torch.zeros(n, device=dev)
 
         def fused():
             eng(reps)
 
-        def generic():
-            with torch.no_grad():
-                ops.replica_mean(reps, avg, divisor=1.0)
-                coll.all_reduce_(avg)
-                ops.replica_mean(avg, avg, divisor=float(K))
-            opt.zero_grad()
-            master.grad = master.detach() - avg.float()
-            opt.step()
-            with torch.no_grad():
-                reps.copy_(master.detach().to(reps.dtype).unsqueeze(0).expand_as(reps))
-
         def sgd():
             ops.diloco_outer(reps, sgd_master, sgd_mom, reps, n, K, SGD["lr"], SGD["momentum"], SGD["dampening"],
                              SGD["weight_decay"], SGD["nesterov"], False)
 
-        pairs = [(timed(fused, a.reps), timed(generic, a.reps)) for _ in range(a.pairs)]
+        pairs = [(timed(fused, a.reps), timed(lambda: generic(reps), a.reps)) for _ in range(a.pairs)]
         sgd_pairs = [(timed(fused, a.reps), timed(sgd, a.reps)) for _ in range(a.pairs)]
         ms_a = sum(x for x, _ in pairs) / len(pairs)
         ms_b = sum(y for _, y in pairs) / len(pairs)
@@ -118,7 +107,7 @@ def main():
         print(line, flush=True)
         with open(a.out, "a") as f:
             f.write(line + "\n")
-        del reps, eng, master, opt, avg, sgd_master, sgd_mom
+        del reps, eng, generic, sgd_master, sgd_mom
         torch.cuda.empty_cache()
 
 
