@@ -607,6 +607,9 @@ def grad_clip_coef(grad, n, max_norm, partials, out):
     g2 = _as2d(grad)
     _gpu(g2, partials, out)
     K, ld = _rows_ld(g2)
+    n = int(n)
+    if n < 0 or n > g2.shape[1]:
+        raise ValueError("grad_clip_coef: n exceeds the row length (ld < n)")
     if partials.numel() < K * lib().ga_sumsq_partials_count() or out.numel() < 2 * K or out.dtype != torch.float32:
         raise ValueError("grad_clip_coef: partials/out too small")
     check(lib().ga_grad_clip_coef(_dtype_code(g2), _p(g2), K, ld, int(n), float(max_norm), _p(partials), _p(out),
@@ -620,6 +623,8 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lerp_w, beta2, one_m_beta2, eps,
     ts, K, ld = _one_layout((param, grad, exp_avg, exp_avg_sq), clip_coef,
                             "adam_step: param/grad/exp_avg/exp_avg_sq must be fp32 replica sets of one layout")
     n = ts[0].shape[1] if n is None else int(n)
+    if n < 0 or n > ts[0].shape[1]:
+        raise ValueError("adam_step: n exceeds the row length (ld < n)")
     if clip_coef is not None and clip_coef.numel() < 2 * K:
         raise ValueError("adam_step: clip_coef must hold 2 floats per replica")
     check(lib().ga_adam_step(_GA_F32, _p(ts[0]), _p(ts[1]), _p(ts[2]), _p(ts[3]), K, ld, n, float(lerp_w),

@@ -9,7 +9,9 @@ torch/optim/adam.py `_multi_tensor_adam` (AdamW = decoupled weight decay)
 and torch/nn/utils/clip_grad.py.  Restated in numpy fp32 in torch's op order;
 `a + s*b` forms that ATen evaluates with a fused multiply-add are evaluated
 exactly and rounded once.  Pinned against torch.optim.AdamW / clip_grad_norm_
-run here (tests/test_oracle_golden.py).
+run here (tests/test_oracle_golden.py).  `sgd_step` is the "sgd" inner
+optimizer (torch.optim.SGD, torch/optim/sgd.py `_single_tensor_sgd`) in the same
+style, pinned against torch.optim.SGD on the CPU (tests/test_oracle_sgd.py).
 """
 import numpy as np
 
@@ -63,3 +65,33 @@ def _adam_step(p, g, m, v, step, lr, betas, eps, weight_decay, decoupled, clip):
     denom = ((np.sqrt(v).astype(f32) / f32(bc2 ** 0.5)).astype(f32) + f32(eps)).astype(f32)
     p = _fma(step_size, (m / denom).astype(f32), p)
     return p, g, m, v
+
+
+def sgd_step(p, g, buf, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, first=False, clip=None):
+    """One torch.optim.SGD step on fp32 arrays (torch/optim/sgd.py `_single_tensor_sgd`:
+    `grad.add(param, alpha=wd)`, `buf = clone(grad)` on the parameter's first step, else
+    `buf.mul_(momentum).add_(grad, alpha=1 - dampening)`, `grad.add(buf, alpha=momentum)`
+    for Nesterov, `param.add_(grad, alpha=-lr)`; every `a + s*b` rounded once).  The
+    scalars are rounded to fp32 once, -lr and 1 - dampening computed in double first.
+    `clip` as in adam_step.  buf is not read on a first step or without momentum (it may
+    be None) and comes back as given without momentum.
+    Returns (p, g_left, buf): g_left is the clipped gradient, which is what stays behind."""
+    with np.errstate(over="ignore", invalid="ignore"):  # non-finite gradients are part of the contract
+        return _sgd_step(p, g, buf, lr, momentum, dampening, weight_decay, nesterov, first, clip)
+
+
+def _sgd_step(p, g, buf, lr, momentum, dampening, weight_decay, nesterov, first, clip):
+    p, g = np.asarray(p, f32).copy(), np.asarray(g, f32).copy()
+    if clip is not None and not clip >= 1.0:
+        g = (g * f32(clip)).astype(f32)
+    g_left = g
+    if weight_decay != 0:
+        g = _fma(f32(weight_decay), p, g)
+    if momentum != 0:
+        if first:
+            buf = g.copy()
+        else:
+            buf = _fma(f32(1 - dampening), g, (np.asarray(buf, f32) * f32(momentum)).astype(f32))
+        g = _fma(f32(momentum), buf, g) if nesterov else buf
+    p = _fma(f32(-lr), g, p)
+    return p, g_left, buf

@@ -13,7 +13,7 @@ import torch
 from oracle import optim as ooptim
 from oracle import reduce as oreduce
 
-P_TOL = dict(rtol=1e-5, atol=1e-7)  # master: check_adam_replica's, tests/test_gpu_stream_kernels.py
+P_TOL = dict(rtol=1e-5, atol=1e-7)  # master: check_adam_replica's, tests/sgd_kernel_checks.py
 M_TOL = dict(rtol=1e-6, atol=0)     # exp_avg / exp_avg_sq
 
 

@@ -22,16 +22,16 @@ import pytest
 import torch
 
 from oracle import diloco as odiloco
-from oracle import optim as ooptim
 from oracle import reduce as oreduce
+# buffers inside sentinel-filled allocations and the Adam / clip bars, shared with test_gpu_sgd_kernel.py
+from sgd_kernel_checks import (DEV, LD_ADAM, N_ADAM, SENT, Placed, adam_data, adam_hp, bits, check_adam_replica,
+                               check_clip, host)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 f32 = np.float32
 N_VEC = 2 * 4096 + 4 * 37  # 8340: 2085 vectors = two full workgroups + 37 vectors
 N_SCALAR = 2 * 1024 + 37   # 2085: odd, so the launcher takes the scalar kernels
-SENT = -7.25               # exact in fp32 and bf16
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -40,60 +40,6 @@ def _gpu():
         pytest.skip("no GPU")
     from gym_amd import _lib
     _lib.lib()
-
-
-def t(a, dtype=torch.float32):
-    return torch.as_tensor(np.ascontiguousarray(a)).to(DEV, dtype)
-
-
-def host(x):
-    torch.cuda.synchronize()
-    return x.float().cpu().numpy()
-
-
-def bits(x):
-    """The tensor's bit patterns on the host (int32 for fp32, int16 for bf16)."""
-    torch.cuda.synchronize()
-    return x.contiguous().view(torch.int32 if x.element_size() == 4 else torch.int16).cpu().numpy()
-
-
-class Placed:
-    """`data` ([n] or [K, n], fp32 values) inside a longer sentinel-filled allocation:
-    `off` sentinel elements, K rows of stride ld >= n, `pad` sentinel elements.
-    .view is what the kernel gets: the [K, n] rows (stride ld), or for 1-D data the
-    buffer from `off` on (n elements and the pad behind them)."""
-
-    def __init__(self, data, ld=None, off=0, pad=64, dtype=torch.float32):
-        a = np.asarray(data, f32)
-        rows = a.reshape(-1, a.shape[-1])
-        self.K, self.n = rows.shape
-        ld = self.n if ld is None else ld
-        assert ld >= self.n
-        self.buf = torch.full((off + self.K * ld + pad,), SENT, dtype=dtype, device=DEV)
-        body = self.buf[off:off + self.K * ld].view(self.K, ld)
-        body[:, :self.n] = t(rows, dtype)
-        self.rows = body[:, :self.n]
-        self.view = self.rows if a.ndim == 2 else self.buf[off:]
-        self.inside = np.zeros(self.buf.numel(), bool)
-        for k in range(self.K):
-            self.inside[off + k * ld:off + k * ld + self.n] = True
-        self.one_d = a.ndim == 1
-        self.before = bits(self.buf)
-
-    def data(self):
-        x = host(self.rows).copy()
-        return x[0] if self.one_d else x
-
-    def data_bits(self):
-        x = bits(self.rows)
-        return x[0] if self.one_d else x
-
-    def outside_untouched(self):
-        b = bits(self.buf)
-        return np.array_equal(b[~self.inside], self.before[~self.inside])
-
-    def untouched(self):
-        return np.array_equal(bits(self.buf), self.before)
 
 
 def rounded_bf16_bits(x):
@@ -447,18 +393,6 @@ def _clip_rows():
     return x
 
 
-def check_clip(out, rows_f64, max_norm):
-    """The bars of test_gpu_optim.test_clip_coef_kernel against the float64 norm."""
-    out = host(out)
-    for k, row in enumerate(rows_f64):
-        ref = math.sqrt(float(np.sum(row * row)))
-        coef = min(1.0, max_norm / (ref + 1e-6))
-        print(f"clip replica {k}: norm {out[2 * k + 1]!r} vs {ref!r}, coef {out[2 * k]!r} vs {coef!r}")
-        assert abs(out[2 * k + 1] - ref) <= 1e-5 * ref
-        assert abs(out[2 * k] - coef) <= 1e-5
-    return out
-
-
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 @pytest.mark.parametrize("ld", [N_CLIP + 5, N_CLIP + 6], ids=["ld-n+5", "ld-odd"])
 def test_clip_coef_three_replicas_two_trips(ld, dtype):
@@ -491,46 +425,7 @@ def test_clip_coef_tiny_and_zero_gradients(n):
 
 
 # ---------------------------------------------------------------- Adam --------
-N_ADAM, LD_ADAM = 8343, 8352  # 2085 float4 = two workgroups + a partial one, and a 3-element tail
-ADAM_SCALES = (1e-3, 0.05, 0.5)  # gradient norms ~ 0.09, 4.6, 46 against max_norm 1: replica 0 is not clipped
-
-
-def adam_hp(lr, betas, eps, wd, decoupled, step):
-    """The launch parameters as ArenaAdam.step computes them."""
-    b1, b2 = betas
-    return dict(lerp_w=1 - b1, beta2=b2, one_m_beta2=1 - b2, eps=eps,
-                wd_factor=(1 - lr * wd) if (decoupled and wd != 0) else 1.0,
-                l2_wd=wd if (not decoupled and wd != 0) else 0.0, step_size=-(lr / (1 - b1 ** step)),
-                bc2_sqrt=math.sqrt(1 - b2 ** step))
-
-
-def adam_data(seed, K=3, n=N_ADAM, zero_state=False):
-    rng = np.random.default_rng(seed)
-    p = (rng.standard_normal((K, n)) * 0.02).astype(f32)
-    g = (rng.standard_normal((K, n)) * np.array(ADAM_SCALES[:K], f32)[:, None]).astype(f32)
-    m = (rng.standard_normal((K, n)) * 0.01).astype(f32)
-    v = (rng.random((K, n)) * 1e-4 + 1e-8).astype(f32)
-    if zero_state:
-        m[:], v[:] = 0, 0
-    return p, g, m, v
-
-
-def check_adam_replica(got, start, coef, step, kw, tag):
-    """One replica of a fused step against oracle.optim.adam_step fed the coefficient the
-    device wrote: p at rtol 1e-5 / atol 1e-7, m and v at rtol 1e-6, the gradient left
-    behind bit-equal to fp32(g * coef) when clipped and bit-unchanged otherwise."""
-    p0, g0, m0, v0 = start
-    gp, gg, gm, gv = got
-    wp, _, wm, wv = ooptim.adam_step(p0, g0, m0, v0, step, clip=coef, **kw)
-    print(f"{tag}: coef {coef!r}; bit-identical share p {(gp == wp).mean():.6f} m {(gm == wm).mean():.6f} "
-          f"v {(gv == wv).mean():.6f}")
-    np.testing.assert_allclose(gp, wp, rtol=1e-5, atol=1e-7)
-    np.testing.assert_allclose(gm, wm, rtol=1e-6, atol=0)
-    np.testing.assert_allclose(gv, wv, rtol=1e-6, atol=0)
-    left = (g0 * f32(coef)).astype(f32) if coef < 1.0 else g0
-    assert np.array_equal(gg.view(np.int32), left.view(np.int32))
-
-
+# N_ADAM = 8343, LD_ADAM = 8352: 2085 float4 = two workgroups + a partial one, and a 3-element tail
 @pytest.mark.parametrize("betas", [(0.9, 0.999), (0.3, 0.9)], ids=["beta1-0.9", "beta1-0.3"])
 @pytest.mark.parametrize("step", [1, 4])
 @pytest.mark.parametrize("decoupled", [True, False], ids=["adamw", "adam-l2"])
