@@ -10,6 +10,7 @@ node count is K_total = world * K_local.
   MeanReduce   SimpleReduce grads, FedAvg params     strategy.py:128-142, federated_averaging.py:53-69
   DiLoCoOuter  fused outer SGD/Nesterov step        diloco.py:34-76
   DiLoCoOuterAdam  the same with an Adam/AdamW update  diloco.py:26-28
+  DiLoCoOuterQuant  the SGD outer step on int8 / int4 block-quantised pseudo-gradients
   TorchOuter   any other outer optimizer: torch's, on an fp32 master
   Sparta       sparse average (Philox or mask)      sparta.py:24-44
   DeMoCodec    DCT encode/top-k + gather + decode   demo_impl/demo.py:142-209
@@ -524,6 +525,69 @@ class TorchOuter:
         self.master.grad = self.master.detach() - self.avg.float()
         self.optimizer.step()
         reps.copy_(self.master.detach())  # broadcast over the rows
+
+
+QUANT_BITS = {"int8": 8, "int4": 4}  # the outer_compression strings of the strategies
+
+
+class DiLoCoOuterQuant:
+    """DiLoCo's outer step (SGD family) on int8 / int4 block-quantised
+    pseudo-gradients, with DiLoCoOuter's call surface.
+
+    Every node quantises its own pseudo-gradient master - x_k in 256-element
+    blocks with one fp32 scale each (ga_quant_encode), the payload rows are
+    all-gathered in node order, and one launch per process decodes all K_total
+    rows in ascending node order, averages them and takes the outer update
+    (ga_diloco_outer_dequant).  Every process decodes the same bytes in the same
+    order, so all nodes end bit-identical without a broadcast.
+
+    Master and momentum are fp32 and REPLICATED on every process, not sharded as
+    DiLoCoOuter's: a rank needs the whole master to form its own delta (8 B per
+    parameter per rank).  error_feedback keeps a [K_local, n] fp32 residual: what
+    quantisation dropped from a node's delta is added to its next one.  No
+    placement search and no masked (SPARTA boundary) step."""
+
+    def __init__(self, coll: Collective, K_local, n, device, dtype, bits=8, error_feedback=False, lr=0.7,
+                 momentum=0.9, nesterov=True, dampening=0.0, weight_decay=0.0, placement=True):
+        if bits not in (4, 8):
+            raise ValueError(f"DiLoCoOuterQuant: bits={bits!r} is not 4 or 8")
+        self.coll, self.K_local, self.n, self.bits = coll, int(K_local), int(n), int(bits)
+        self.K_total = coll.world * self.K_local
+        self.hp = dict(lr=lr, momentum=momentum, nesterov=nesterov, dampening=dampening, weight_decay=weight_decay)
+        self.shard, self.per, self.dtype = False, self.n, dtype
+        self._state = torch.zeros((2 if momentum != 0 else 1) * self.n, device=device, dtype=torch.float32)
+        self.master = self._state[:self.n]
+        self.mom = self._state[self.n:] if momentum != 0 else None
+        self.residual = (torch.zeros(self.K_local, self.n, device=device, dtype=torch.float32)
+                         if error_feedback else None)
+        self.payload_bytes_per_node = ops.quant_row_bytes(self.n, self.bits)
+        self.payload = torch.zeros(self.K_total, self.payload_bytes_per_node, device=device, dtype=torch.uint8)
+        self.placement = {"placed": False, "why": "no search for the quantised outer step"}
+        self.relocate_replicas = None  # accepted as on DiLoCoOuter; the set stays where it is
+        self.first = True
+        self.launch_elems = []  # elements per ga_diloco_outer_dequant launch of the last step
+
+    def init_master(self, params_flat):
+        """master <- the node's initial parameters (diloco.py:81-82); no error carried over."""
+        self.master.copy_(params_flat[:self.n])
+        if self.residual is not None:
+            self.residual.zero_()
+        self.first = True
+
+    def __call__(self, reps, sparse_mask=None):
+        if sparse_mask is not None:
+            raise ValueError("DiLoCoOuterQuant: no one-pass masked outer step; run Sparta and the outer step one "
+                             "after the other")
+        n, K, h = self.n, self.K_local, self.hp
+        a = self.coll.rank * K
+        own = self.payload[a:a + K]
+        ops.quant_encode(reps[:, :n], self.master, self.residual, own, n, self.bits)
+        if self.coll.exchange:
+            self.coll.all_gather_into(self.payload.view(-1), own.view(-1))
+        ops.diloco_outer_dequant(self.payload, self.master, self.mom, reps[:, :n], n, self.bits, self.K_total,
+                                 h["lr"], h["momentum"], h["dampening"], h["weight_decay"], h["nesterov"], self.first)
+        self.launch_elems = [n]
+        self.first = False
 
 
 def sparta_capacity(n, p):

@@ -239,6 +239,75 @@ def diloco_outer_adam_masked(reps, bits, master, exp_avg, exp_avg_sq, n, sparse_
           "ga_diloco_outer_adam_masked")
 
 
+def quant_row_bytes(n, bits):
+    """Bytes of one int8 / int4 payload row of n elements (ga_quant_row_bytes: 256-element
+    blocks, q bytes then one fp32 scale per block, rounded up to 16)."""
+    nbytes = int(lib().ga_quant_row_bytes(int(n), int(bits)))
+    if nbytes < 0:
+        raise ValueError(f"quant_row_bytes: n={n} must be >= 0 and bits={bits} 4 or 8")
+    return nbytes
+
+
+def _payload_ld(who, payload, rows, n, bits):
+    if payload.dtype != torch.uint8 or payload.dim() != 2 or payload.stride(1) != 1:
+        raise TypeError(f"{who}: the payload is a 2-D uint8 tensor with contiguous rows")
+    if payload.shape[0] != rows:
+        raise ValueError(f"{who}: {payload.shape[0]} payload rows for {rows} rows")
+    need = quant_row_bytes(n, bits)
+    ld = payload.stride(0) if rows > 1 else max(payload.shape[1], need) // 16 * 16
+    if payload.shape[1] < need or ld < need:
+        raise ValueError(f"{who}: payload rows of {payload.shape[1]} bytes, {need} needed")
+    return ld
+
+
+def quant_encode(x, master, residual, payload, n, bits):
+    """payload[k] <- the int8 / int4 block-quantised pseudo-gradient master - x[k]
+    (+ residual[k], which then takes the quantisation error) of every row k of the
+    replica set x (ga_quant_encode; payload: uint8 [K, >= quant_row_bytes(n, bits)])."""
+    x2 = _as2d(x)
+    r2 = _as2d(residual) if residual is not None else None
+    _gpu(x2, master, r2, payload)
+    K, ldx = _rows_ld(x2)
+    n = int(n)
+    if n < 0 or x2.shape[1] < n or master.numel() < n or (r2 is not None and r2.shape[1] < n):
+        raise ValueError("quant_encode: buffers shorter than n")
+    if master.dtype != torch.float32 or not master.is_contiguous():
+        raise TypeError("quant_encode: master must be a contiguous float32 tensor")
+    ldr = 0
+    if r2 is not None:
+        if r2.dtype != torch.float32 or r2.shape[0] != K:
+            raise TypeError("quant_encode: the residual is a float32 set with one row per row of x")
+        ldr = _rows_ld(r2)[1]
+    ldq = _payload_ld("quant_encode", payload, K, n, bits)
+    check(lib().ga_quant_encode(_dtype_code(x2), _p(x2), K, ldx, _p(master), _p(r2), ldr, n, int(bits), _p(payload),
+                                ldq, _stream()), "ga_quant_encode")
+
+
+def diloco_outer_dequant(payload, master, mom, dst, n, bits, divisor, lr, momentum, dampening, weight_decay, nesterov,
+                         first_step):
+    """The DiLoCo outer step on the sum of the S dequantised payload rows over divisor
+    (ga_diloco_outer_dequant): master / mom (fp32) updated as by diloco_outer, every
+    row of dst <- the new master."""
+    dst2 = _as2d(dst) if dst is not None else None
+    _gpu(payload, master, mom, dst2)
+    n = int(n)
+    Ko, ldd = _rows_ld(dst2) if dst2 is not None else (0, 0)
+    if n < 0 or master.numel() < n or (mom is not None and mom.numel() < n):
+        raise ValueError("diloco_outer_dequant: buffers shorter than n")
+    if dst2 is not None and dst2.shape[1] < n:
+        raise ValueError("diloco_outer_dequant: dst shorter than n")
+    for t in (master, mom):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError("diloco_outer_dequant: master and momentum must be contiguous float32 tensors")
+    S = payload.shape[0] if payload.dim() == 2 else -1
+    ldq = _payload_ld("diloco_outer_dequant", payload, S, n, bits)
+    code = _dtype_code(dst2) if dst2 is not None else _lib.GA_F32
+    check(lib().ga_diloco_outer_dequant(_p(payload), S, ldq, int(bits), n, float(divisor), _p(master), _p(mom),
+                                        int(bool(first_step)), float(lr), float(momentum), float(dampening),
+                                        float(weight_decay), int(bool(nesterov)), code, _p(dst2), Ko, ldd,
+                                        _stream()), "ga_diloco_outer_dequant")
+
+
 def sparta_gap_table(p):
     """The 64-entry gap table of the Philox mask stream (include/gym_amd.h)."""
     import ctypes

@@ -48,7 +48,7 @@ from torch.utils.data import DataLoader
 from . import ops
 from .arena import ReplicaArena
 from .comm import Collective
-from .engine import DiLoCoOuter, MeanReduce, demo_codec, node_mean
+from .engine import DiLoCoOuter, DiLoCoOuterQuant, MeanReduce, demo_codec, node_mean
 from .fused_optim import build_fused
 from .strategy.demo import DeMoStrategy
 from .strategy.diloco import DiLoCoStrategy, build_outer_engine
@@ -182,7 +182,7 @@ class ReplicaRunner:
                 self.fuse = bool(s.fuse_boundary and not self.sparta.philox and not self.coll.exchange
                                  and isinstance(self.outer, DiLoCoOuter))
                 s.fuse_boundary = self.fuse
-                if isinstance(self.outer, DiLoCoOuter):
+                if isinstance(self.outer, (DiLoCoOuter, DiLoCoOuterQuant)):
                     s.engine = self.outer  # Strategy.placement_records reads the outer step's record there
         # the strategy's LR schedule on every optimizer (strategy.py:75-112)
         for o in (self.optim.opts if isinstance(self.optim, _PerNodeOptim) else [self.optim]):

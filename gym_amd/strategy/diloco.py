@@ -16,15 +16,21 @@ with an Adam update (ga_diloco_outer_adam, master and both moments sharded;
 fused_outer=False keeps torch's optimizer).  Any other outer optimizer class
 runs torch's optimizer on a GPU master copy (replicated on every rank) fed by
 the same averaging kernel (engine.TorchOuter).  build_outer_engine picks among
-the three for both modes -- one node per process here, K nodes per process in
+them for both modes -- one node per process here, K nodes per process in
 gym_amd.replica -- so neither holds outer-step arithmetic of its own.
+
+outer_compression="int8" | "int4" (default None) exchanges the pseudo-gradients
+block-quantised instead of in fp32 (engine.DiLoCoOuterQuant: ga_quant_encode, one
+all-gather of the payload rows, ga_diloco_outer_dequant), outer_error_feedback=True
+carries each node's quantisation error into its next outer step.  SGD-family outer
+optimizers only; the master and momentum are then replicated on every rank.
 """
 from typing import Optional, Union
 
 import torch
 
 from .. import ops
-from ..engine import DiLoCoOuter, DiLoCoOuterAdam, TorchOuter
+from ..engine import QUANT_BITS, DiLoCoOuter, DiLoCoOuterAdam, DiLoCoOuterQuant, TorchOuter
 from .communicate_optimize_strategy import CommunicationModule
 from .optim import OptimSpec, ensure_optim_spec
 from .strategy import Strategy, build_inner_optimizer, clip_and_step
@@ -73,14 +79,33 @@ def fused_adam_hparams(spec: OptimSpec):
                 weight_decay=float(weight_decay), decoupled=decoupled)
 
 
+def check_outer_compression(compression, spec):
+    """The bit width of outer_compression (None: off) for outer OptimSpec `spec`;
+    ValueError for an unknown string or an outer optimizer without a quantised step."""
+    if compression is None:
+        return None
+    if compression not in QUANT_BITS:
+        raise ValueError(f"outer_compression={compression!r}: expected None, " + " or ".join(map(repr, QUANT_BITS)))
+    if fused_sgd_hparams(spec) is None:
+        raise ValueError(f"outer_compression={compression!r} needs a plain torch.optim.SGD outer optimizer (the "
+                         f"quantised outer step has no other update); got {spec.cls.__name__} with "
+                         f"{dict(spec.kwargs or {})}")
+    return QUANT_BITS[compression]
+
+
 def build_outer_engine(strategy, spec, coll, K_local, n, device, dtype):
     """The outer step of outer OptimSpec `spec` over a [K_local, n] set:
     DiLoCoOuter for plain SGD, DiLoCoOuterAdam for Adam / AdamW unless the
     strategy was built with fused_outer=False (the A/B switch against torch's
     optimizer; SGD specs are always fused), TorchOuter (torch's optimizer on an
-    fp32 master) for every other spec."""
+    fp32 master) for every other spec.  With outer_compression set:
+    DiLoCoOuterQuant for plain SGD, ValueError for anything else."""
     placement = strategy.placement_opt
+    bits = check_outer_compression(strategy.kwargs.get("outer_compression"), spec)
     hp = fused_sgd_hparams(spec)
+    if bits is not None:
+        return DiLoCoOuterQuant(coll, K_local, n, device, dtype, bits=bits, placement=placement,
+                                error_feedback=bool(strategy.kwargs.get("outer_error_feedback", False)), **hp)
     if hp is not None:
         return DiLoCoOuter(coll, K_local, n, device, dtype, placement=placement, **hp)
     hp = fused_adam_hparams(spec) if strategy.kwargs.get("fused_outer", True) else None
@@ -135,11 +160,15 @@ class DiLoCoCommunicator(CommunicationModule):
 
 class DiLoCoStrategy(Strategy):
     def __init__(self, optim_spec: Optional[Union[str, OptimSpec]] = None,
-                 outer_optim_spec: Optional[Union[str, OptimSpec]] = None, H: int = 100, **kwargs):
+                 outer_optim_spec: Optional[Union[str, OptimSpec]] = None, H: int = 100,
+                 outer_compression: Optional[str] = None, outer_error_feedback: bool = False, **kwargs):
         self.inner_optim_spec = ensure_optim_spec(optim_spec, OptimSpec(torch.optim.AdamW))
         self.outer_optim_spec = ensure_optim_spec(outer_optim_spec, default_outer_spec())
         self.H = H
-        super().__init__(**kwargs)
+        check_outer_compression(outer_compression, self.outer_optim_spec)
+        # both reach build_outer_engine through self.kwargs, as fused_outer does
+        super().__init__(outer_compression=outer_compression, outer_error_feedback=bool(outer_error_feedback),
+                         **kwargs)
 
     def _init_node(self, model, rank, num_nodes):
         super()._init_node(model, rank, num_nodes)

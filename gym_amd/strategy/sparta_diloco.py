@@ -19,11 +19,16 @@ average the outer step forms, so the two run as ONE pass
 (ga_diloco_outer_masked) with bit-identical results.  mask_source="philox"
 keeps no mask in memory: its boundary steps run the two launches and
 fuse_boundary reads False.
+
+outer_compression= / outer_error_feedback= as on DiLoCoStrategy (int8 / int4
+block-quantised pseudo-gradients, SGD-family outer optimizers).  The quantised
+outer step has no masked form: the two modules run in sequence and
+fuse_boundary reads False.
 """
 from typing import Optional, Union
 
 from .communicate_optimize_strategy import CommunicateOptimizeStrategy
-from .diloco import DiLoCoCommunicator
+from .diloco import DiLoCoCommunicator, check_outer_compression
 from .optim import OptimSpec
 from .sparta import RandomIndexSelector, SparseCommunicator
 
@@ -31,14 +36,18 @@ from .sparta import RandomIndexSelector, SparseCommunicator
 class SPARTADiLoCoStrategy(CommunicateOptimizeStrategy):
     def __init__(self, inner_optim: Optional[Union[str, OptimSpec]] = None,
                  outer_optim: Optional[Union[str, OptimSpec]] = None, p_sparta: float = 0.005, H: int = 100,
-                 mask_source="torch", fuse_boundary=True, **kwargs):
+                 mask_source="torch", fuse_boundary=True, outer_compression: Optional[str] = None,
+                 outer_error_feedback: bool = False, **kwargs):
         index_selector = RandomIndexSelector(p_sparta, mask_source=mask_source)
         sparse_comm = SparseCommunicator(index_selector)
         diloco_comm = DiLoCoCommunicator(H=H, outer_optim=outer_optim)
-        super().__init__(communication_modules=[sparse_comm, diloco_comm], inner_optim=inner_optim, **kwargs)
+        check_outer_compression(outer_compression, diloco_comm.outer_optim_spec)
+        super().__init__(communication_modules=[sparse_comm, diloco_comm], inner_optim=inner_optim,
+                         outer_compression=outer_compression, outer_error_feedback=bool(outer_error_feedback),
+                         **kwargs)
         self.index_selector = index_selector
         self.p_sparta = p_sparta
         self.H = H
         self.outer_optim_spec = diloco_comm.outer_optim_spec
-        self.fuse_boundary = bool(fuse_boundary) and mask_source != "philox"
+        self.fuse_boundary = bool(fuse_boundary) and mask_source != "philox" and outer_compression is None
         self.mask_draw = None  # which mask draw the last step ran ("philox" | "fused" | "torch")

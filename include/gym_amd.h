@@ -264,6 +264,61 @@ GA_API int ga_diloco_outer_adam_masked(int dtype, void* src, int64_t K, int64_t 
                                        float l2_wd, float step_size, float bc2_sqrt, void* dst,
                                        int64_t K_out, int64_t ld_dst, hipStream_t stream);
 
+/* ---- DiLoCo outer step on int8 / int4 block-quantised pseudo-gradients --- */
+
+/*
+ * The quantised format, on the wire and in memory (no reference counterpart: the
+ * reference's outer step all-reduces fp32, diloco.py:34-37).  Blocks are 256
+ * consecutive elements of an arena row, nb = ceil(n / 256), the last may be short;
+ * bits is 8 or 4, qmax 127 or 7.  One payload row per node, in bytes:
+ *   [ q : nb * 256 * bits / 8 ][ scales : nb x fp32 ]
+ * int8: one two's-complement byte per element; int4: byte j of a block holds
+ * element 2j in bits 0-3 and element 2j + 1 in bits 4-7 (two's-complement nibbles).
+ * Elements past n in the last block and the pad bytes are 0.
+ * ga_quant_row_bytes: that size rounded up to a multiple of 16 (host only; -1 for
+ * n < 0 or bits outside {4, 8}).
+ */
+GA_API int64_t ga_quant_row_bytes(int64_t n, int bits);
+
+/*
+ * Encode the pseudo-gradients of K rows x [K, ld_x] (f32 / bf16) against an fp32
+ * master into K payload rows (row k at payload + k * ld_q_bytes).  Every line is one
+ * individually rounded fp32 operation:
+ *   d    = master[i] - float(x[k, i])
+ *   d    = d + residual[k, i]                  (residual != null: error feedback)
+ *   amax = max over the block of |d|
+ *   !(amax >= 2^-100):  s = 0 and every q of the block = 0
+ *   else  s = amax / qmax, inv = qmax / amax   (IEEE fp32 divisions)
+ *         q = clamp((int)rintf(d * inv), -qmax, qmax)
+ *   scales[k, b] = s
+ *   residual[k, i] = d - float(q) * s          (residual != null; mul, then sub)
+ * residual is an fp32 [K, ld_r] set or null.  ld_q_bytes >= ga_quant_row_bytes(n,
+ * bits) and a multiple of 16, payload 16-byte aligned; bytes of a payload row past
+ * its row_bytes are not written.  x / master / residual may have any element
+ * alignment and ld (16-byte vector access when aligned, element access otherwise,
+ * the same bytes either way).  Only finite inputs are in contract: a non-finite
+ * value does not fault, its block's result is unspecified.
+ */
+GA_API int ga_quant_encode(int dtype, const void* x, int64_t K, int64_t ld_x, const float* master,
+                           float* residual, int64_t ld_r, int64_t n, int bits, void* payload,
+                           int64_t ld_q_bytes, hipStream_t stream);
+
+/*
+ * Decode S payload rows (ga_quant_encode's format, row r at payload + r *
+ * ld_q_bytes, node order) and take the outer step, one pass over n elements:
+ *   acc = 0; for r in 0..S-1: acc = acc + float(q_r[i]) * s_r[block of i]
+ *   g   = acc / divisor
+ *   ga_diloco_outer's update from its pseudo-gradient on (weight decay, first step,
+ *   momentum, dampening, Nesterov, master -= lr * g) on the fp32 master / mom
+ *   dst_j[i] = master[i] rounded to `dtype`  for j < K_out
+ * S has no upper limit.  mom may be null when momentum == 0.  Algorithmic bytes per
+ * element: S * (bits / 8 + 1 / 64) + 16 (8 without momentum) + K_out * sizeof(dtype).
+ */
+GA_API int ga_diloco_outer_dequant(const void* payload, int64_t S, int64_t ld_q_bytes, int bits, int64_t n,
+                                   float divisor, float* master, float* mom, int first_step, float lr,
+                                   float momentum, float dampening, float weight_decay, int nesterov, int dtype,
+                                   void* dst, int64_t K_out, int64_t ld_dst, hipStream_t stream);
+
 /* ---- SPARTA sparse averaging ------------------------------------------- */
 
 /* Workspace bytes needed by ga_sparta_select for an arena of n elements. */
