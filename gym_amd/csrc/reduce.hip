@@ -14,10 +14,12 @@
 // lane reads every replica of its vector before it writes any, and no two
 // lanes touch the same vector, so the sources carry no __restrict__.
 //
-// The outer step exists twice: diloco_outer_kernel (SGD / Nesterov on the
-// pseudo-gradient, ga_diloco_outer[_masked]) and diloco_outer_adam_kernel (Adam /
+// The outer step exists three times: diloco_outer_kernel (SGD / Nesterov on the
+// pseudo-gradient, ga_diloco_outer[_masked]), diloco_outer_adam_kernel (Adam /
 // AdamW, ga_diloco_outer_adam[_masked]: one more fp32 state stream, adam_math.h's
-// element update).  They share the geometry, the selectors and the helpers below.
+// element update) and diloco_outer_merge_kernel (ga_diloco_outer_merge: the SGD step
+// whose result is mixed into the live rows).  They share the geometry and the helpers
+// below, the first two also the selectors.
 #include "ga_common.h"
 #include "adam_math.h"
 
@@ -279,6 +281,105 @@ __global__ __launch_bounds__(kBlock) void diloco_outer_adam_kernel(
     }
 }
 
+// The delayed, mixed merge of the streaming outer step (ga_diloco_outer_merge): the
+// SGD / Nesterov outer update of diloco_outer_kernel on a staged sum (or on the live
+// rows themselves), then every live row x_j <- alpha x_j + (1 - alpha) master instead
+// of master.  The geometry, loads, stores and outer_update of diloco_outer_kernel; fp32
+// master and momentum.  With alpha != 0 a lane loads up to kMergeRows rows of x back to
+// back (the first group together with master and momentum, before the lane's first
+// store), blends and stores them, then the next group.  x may alias src (same base, ld
+// and row count): every source of a vector is read before any of the vector's stores,
+// and row j of x is read before it is written and never after.  A sibling rather than
+// a template parameter of diloco_outer_kernel, so that kernel's machine code stays what
+// the headline measurement ran.
+constexpr int kMergeRows = 4;
+
+template <typename T, bool VEC, bool MIX>
+__global__ __launch_bounds__(kBlock) void diloco_outer_merge_kernel(
+    const T* src, int64_t K, int64_t ld_src, int64_t n, float* master, float* mom, OuterParams op, float alpha,
+    T* x, int64_t K_out, int64_t ld_x) {
+    const bool has_mom = op.momentum != 0.f;
+    constexpr bool mix = MIX;  // alpha != 0; the alpha == 0 instance holds no blend code and no x registers
+    const float keep = 1.f - alpha;
+    int64_t lo, hi;
+    if constexpr (VEC) {
+        using V = typename Vec4<T>::type;
+        chunk_range(n >> 2, lo, hi);
+        for (int64_t v = lo + threadIdx.x; v < hi; v += kBlock) {
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8
+            for (int64_t k = 0; k < K; ++k) {
+                float f[4];
+                Vec4<T>::unpack(stream_load(reinterpret_cast<const V*>(src + k * ld_src) + v), f);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e] += f[e];
+            }
+            float m[4], b[4] = {0.f, 0.f, 0.f, 0.f};
+            Vec4<float>::unpack(stream_load(reinterpret_cast<const float4*>(master) + v), m);
+            if (has_mom && !op.first_step) Vec4<float>::unpack(stream_load(reinterpret_cast<const float4*>(mom) + v), b);
+            V xs[kMergeRows];
+            if constexpr (mix) {
+#pragma unroll
+                for (int r = 0; r < kMergeRows; ++r)
+                    if (r < K_out) xs[r] = stream_load(reinterpret_cast<const V*>(x + r * ld_x) + v);
+            }
+            float out[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) out[e] = outer_update(acc[e], m[e], b[e], op);
+            // device-scope (sc1) stores based at the workgroup's block of each stream
+            const uint32_t i = (uint32_t)(v - lo);
+            store_sc1(reinterpret_cast<float4*>(master) + lo, i, Vec4<float>::pack(m));
+            if (has_mom) store_sc1(reinterpret_cast<float4*>(mom) + lo, i, Vec4<float>::pack(b));
+            if constexpr (!mix) {
+                const V o = Vec4<T>::pack(out);
+                for (int64_t j = 0; j < K_out; ++j) store_sc1(reinterpret_cast<V*>(x + j * ld_x) + lo, i, o);
+            } else {
+                float part[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) part[e] = keep * out[e];
+                for (int64_t j0 = 0; j0 < K_out; j0 += kMergeRows) {
+                    if (j0 != 0) {
+#pragma unroll
+                        for (int r = 0; r < kMergeRows; ++r)
+                            if (j0 + r < K_out) xs[r] = stream_load(reinterpret_cast<const V*>(x + (j0 + r) * ld_x) + v);
+                    }
+#pragma unroll
+                    for (int r = 0; r < kMergeRows; ++r) {
+                        if (j0 + r < K_out) {
+                            float f[4];
+                            Vec4<T>::unpack(xs[r], f);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) f[e] = fmaf(alpha, f[e], part[e]);
+                            store_sc1(reinterpret_cast<V*>(x + (j0 + r) * ld_x) + lo, i, Vec4<T>::pack(f));
+                        }
+                    }
+                }
+            }
+        }
+    } else {
+        chunk_range(n, lo, hi);
+        for (int64_t i = lo + threadIdx.x; i < hi; i += kBlock) {
+            float acc = 0.f;
+#pragma unroll 4
+            for (int64_t k = 0; k < K; ++k) acc += Elem<T>::load(src + k * ld_src + i);
+            float m = master[i];
+            float b = (has_mom && !op.first_step) ? mom[i] : 0.f;
+            const float out = outer_update(acc, m, b, op);
+            master[i] = m;
+            if (has_mom) mom[i] = b;
+            if constexpr (!mix) {
+                for (int64_t j = 0; j < K_out; ++j) Elem<T>::store(x + j * ld_x + i, out);
+            } else {
+                const float part = keep * out;
+                for (int64_t j = 0; j < K_out; ++j) {
+                    T* p = x + j * ld_x + i;
+                    Elem<T>::store(p, fmaf(alpha, Elem<T>::load(p), part));
+                }
+            }
+        }
+    }
+}
+
 // Placement probe of the fused outer step (no reference counterpart): the exact
 // access pattern of diloco_outer_kernel<float, float, true, DenseSel> -- workgroup b's block
 // of K replica streams, master and momentum read, the same blocks written through
@@ -388,6 +489,22 @@ static int launch_diloco_adam(const char* who, const void* src, int64_t K, int64
     return check_launch(who);
 }
 
+// The merge step's launch; the vector path by launch_diloco's rule.
+template <typename T>
+static int launch_diloco_merge(const void* src, int64_t K, int64_t ld_src, int64_t n, float* master, float* mom,
+                               const OuterParams& op, float alpha, void* x, int64_t K_out, int64_t ld_x,
+                               hipStream_t stream) {
+    const int vb = 4 * (int)sizeof(T);
+    const bool vec = (n % 4 == 0) && (ld_src % 4 == 0) && (ld_x % 4 == 0) && aligned(src, vb) && aligned(x, vb) &&
+                     aligned(master, 16) && aligned(mom, 16);
+    auto* kernel = vec ? (alpha != 0.f ? diloco_outer_merge_kernel<T, true, true> : diloco_outer_merge_kernel<T, true, false>)
+                       : (alpha != 0.f ? diloco_outer_merge_kernel<T, false, true>
+                                       : diloco_outer_merge_kernel<T, false, false>);
+    hipLaunchKernelGGL(kernel, dim3(chunk_grid(vec ? n / 4 : n)), dim3(kBlock), 0, stream, (const T*)src, K, ld_src,
+                       n, master, mom, op, alpha, (T*)x, K_out, ld_x);
+    return check_launch("ga_diloco_outer_merge");
+}
+
 }  // namespace ga
 
 using namespace ga;
@@ -487,6 +604,40 @@ extern "C" GA_API int ga_diloco_outer_masked(int dtype, void* src, int64_t K, in
                                                         stream, sel);
         default:
             set_error("ga_diloco_outer_masked: unknown dtype %d", dtype);
+            return GA_EINVAL;
+    }
+}
+
+extern "C" GA_API int ga_diloco_outer_merge(int dtype, const void* src, int64_t K, int64_t ld_src, int64_t n,
+                                            float divisor, float* master, float* mom, int first_step, float lr,
+                                            float momentum, float dampening, float weight_decay, int nesterov,
+                                            float alpha, void* x, int64_t K_out, int64_t ld_x, hipStream_t stream) {
+    clear_error();
+    GA_REQUIRE(n >= 0 && K >= 1 && K_out >= 0, "ga_diloco_outer_merge: bad sizes n=%lld K=%lld K_out=%lld",
+               (long long)n, (long long)K, (long long)K_out);
+    GA_REQUIRE(alpha >= 0.0f && alpha < 1.0f, "ga_diloco_outer_merge: alpha %g is not in [0, 1)", (double)alpha);
+    if (n == 0) return GA_OK;
+    GA_REQUIRE(src && master, "ga_diloco_outer_merge: null src/master");
+    GA_REQUIRE(K_out == 0 || x, "ga_diloco_outer_merge: null x");
+    GA_REQUIRE(momentum == 0.0f || mom, "ga_diloco_outer_merge: momentum != 0 needs a momentum buffer");
+    GA_REQUIRE(K == 1 || ld_src >= n, "ga_diloco_outer_merge: ld_src < n");
+    GA_REQUIRE(K_out <= 1 || ld_x >= n, "ga_diloco_outer_merge: ld_x < n");
+    GA_REQUIRE(x != src || K_out == 0 || (K_out == K && (K == 1 || ld_x == ld_src)),
+               "ga_diloco_outer_merge: x aliasing src needs K_out == K = %lld and ld_x == ld_src; got K_out=%lld",
+               (long long)K, (long long)K_out);
+    GA_REQUIRE(divisor != 0.0f, "ga_diloco_outer_merge: divisor is 0");
+    GA_REQUIRE(!(nesterov && (momentum <= 0.0f || dampening != 0.0f)),
+               "ga_diloco_outer_merge: Nesterov momentum requires a momentum and zero dampening");
+    OuterParams op{divisor, lr, momentum, dampening, weight_decay, first_step ? 1 : 0, nesterov ? 1 : 0};
+    if (momentum == 0.0f) mom = nullptr;
+    switch (dtype) {
+        case GA_F32:
+            return launch_diloco_merge<float>(src, K, ld_src, n, master, mom, op, alpha, x, K_out, ld_x, stream);
+        case GA_BF16:
+            return launch_diloco_merge<__hip_bfloat16>(src, K, ld_src, n, master, mom, op, alpha, x, K_out, ld_x,
+                                                       stream);
+        default:
+            set_error("ga_diloco_outer_merge: unknown dtype %d", dtype);
             return GA_EINVAL;
     }
 }

@@ -11,6 +11,8 @@ node count is K_total = world * K_local.
   DiLoCoOuter  fused outer SGD/Nesterov step        diloco.py:34-76
   DiLoCoOuterAdam  the same with an Adam/AdamW update  diloco.py:26-28
   DiLoCoOuterQuant  the SGD outer step on int8 / int4 block-quantised pseudo-gradients
+  DiLoCoOuterStream  the SGD outer step sent at one step, merged `delay` steps later and mixed into the rows
+  FragmentedOuter  Streaming DiLoCo's schedule: one outer engine per fragment of the arena (fragment_bounds)
   TorchOuter   any other outer optimizer: torch's, on an fp32 master
   Sparta       sparse average (Philox or mask)      sparta.py:24-44
   DeMoCodec    DCT encode/top-k + gather + decode   demo_impl/demo.py:142-209
@@ -588,6 +590,176 @@ class DiLoCoOuterQuant:
                                  h["lr"], h["momentum"], h["dampening"], h["weight_decay"], h["nesterov"], self.first)
         self.launch_elems = [n]
         self.first = False
+
+
+class DiLoCoOuterStream:
+    """Streaming DiLoCo's outer step (SGD family) for one fragment: the exchange
+    is sent at one step and its result merged `delay` inner steps later, mixed
+    into the live rows instead of overwriting them:
+        x_k <- mix * x_k + (1 - mix) * master        (ga_diloco_outer_merge)
+
+    send(reps) stages the ascending fp32 sum of the local rows in one row of the
+    arena's dtype and starts its all-reduce (async under RCCL: the collective runs
+    on RCCL's stream under the next `delay` inner steps; gloo completes it at
+    once, with the same numerics).  receive(reps) waits for it and makes one merge
+    launch: the outer update on the staged sum over K_total, then the blend into
+    every live row.  Calling the engine is send then receive; with no exchange and
+    no delay that is one in-place launch over the rows and no staging row.
+
+    Master and momentum are fp32 and REPLICATED on every process, not sharded as
+    DiLoCoOuter's (8 B per parameter per rank, plus the staging row; `shard` and
+    `chunks` are accepted as on DiLoCoOuter and ignored).  No placement search and no
+    masked (SPARTA boundary) step."""
+
+    def __init__(self, coll: Collective, K_local, n, device, dtype, lr=0.7, momentum=0.9, nesterov=True,
+                 dampening=0.0, weight_decay=0.0, delay=0, mix=0.0, shard=None, chunks=None, placement=True):
+        if int(delay) != delay or delay < 0:
+            raise ValueError(f"DiLoCoOuterStream: delay={delay!r} is not an integer >= 0")
+        if not 0.0 <= float(mix) < 1.0:
+            raise ValueError(f"DiLoCoOuterStream: mix={mix!r} is not in [0, 1)")
+        self.coll, self.K_local, self.n = coll, int(K_local), int(n)
+        self.K_total = coll.world * self.K_local
+        self.delay, self.mix = int(delay), float(mix)
+        self.hp = dict(lr=lr, momentum=momentum, nesterov=nesterov, dampening=dampening, weight_decay=weight_decay)
+        self.shard, self.per, self.dtype = False, self.n, dtype
+        self._state = torch.zeros((2 if momentum != 0 else 1) * self.n, device=device, dtype=torch.float32)
+        self.master = self._state[:self.n]
+        self.mom = self._state[self.n:] if momentum != 0 else None
+        self.staged = bool(coll.exchange or self.delay > 0)
+        self.stage = torch.zeros(self.n, device=device, dtype=dtype) if self.staged else None
+        self._work = None  # the handle of the exchange in flight
+        self.placement = {"placed": False, "why": "no search for the streaming outer step"}
+        self.relocate_replicas = None  # accepted as on DiLoCoOuter; the set stays where it is
+        self.first = True
+        self.launch_elems = []  # elements per ga_diloco_outer_merge launch of the last receive
+
+    def init_master(self, params_flat):
+        """master <- the node's initial parameters (diloco.py:81-82); nothing in flight."""
+        self.cancel()
+        self.master.copy_(params_flat[:self.n])
+        self.first = True
+
+    def send(self, reps):
+        if not self.staged:
+            return
+        ops.replica_mean(reps[:, :self.n], self.stage, n=self.n, divisor=1.0)
+        self._work = self.coll.all_reduce_(self.stage, async_op=True)
+
+    def receive(self, reps):
+        n, h = self.n, self.hp
+        if self.staged:
+            if self._work is None:
+                raise RuntimeError("DiLoCoOuterStream.receive: nothing was sent")
+            self._work.wait()
+            self._work = None
+            src = self.stage
+        else:
+            src = reps[:, :n]
+        ops.diloco_outer_merge(src, self.master, self.mom, reps[:, :n], n, float(self.K_total), h["lr"],
+                               h["momentum"], h["dampening"], h["weight_decay"], h["nesterov"], self.first, self.mix)
+        self.launch_elems = [n]
+        self.first = False
+
+    def cancel(self):
+        """Wait for an exchange in flight and drop its result."""
+        if self._work is not None:
+            self._work.wait()
+            self._work = None
+
+    def __call__(self, reps, sparse_mask=None):
+        if sparse_mask is not None:
+            raise ValueError("DiLoCoOuterStream: no one-pass masked outer step; run Sparta and the outer step one "
+                             "after the other")
+        self.send(reps)
+        self.receive(reps)
+
+
+def fragment_bounds(offsets, n, F, unit):
+    """[c_0 = 0, c_1, ..., c_F = n]: the arena cut into F fragments at tensor starts.
+    For 0 < f < F, c_f is the start offset of the tensor nearest to f * n / F (a
+    tie goes to the lower offset), rounded down to a multiple of `unit` -- the
+    arena's padding unit, 512 * world elements, so that shard plans, 256-element
+    quantisation blocks and 16-byte vector access hold on every fragment.  A cut
+    that rounding moves inside a tensor is harmless: the outer update is
+    element-wise.  ValueError when the bounds are not strictly increasing."""
+    n, F, unit = int(n), int(F), int(unit)
+    offs = sorted(int(o) for o in offsets)
+    if F < 1 or unit < 1 or not offs:
+        raise ValueError(f"fragment_bounds: F={F}, unit={unit}, {len(offs)} tensors")
+    bounds = [0]
+    for f in range(1, F):
+        # |o - f n / F| compared exactly, as |o F - f n|
+        near = min(offs, key=lambda o: (abs(o * F - f * n), o))
+        bounds.append(near // unit * unit)
+    bounds.append(n)
+    if any(b <= a for a, b in zip(bounds, bounds[1:])):
+        raise ValueError(f"num_fragments too large for this model: {F} fragments of {n} elements in units of {unit} "
+                         f"cut at {bounds}")
+    return bounds
+
+
+class FragmentedOuter:
+    """Streaming DiLoCo's schedule over F fragments [a_f, b_f) of the arena, one
+    outer engine per fragment.  Fragment f takes its outer step when
+        local_step > 0 and (local_step + (f * H) // F) % H == 0
+    so every fragment fires once per H steps, staggered by H / F, and an outer
+    event moves about n / F elements instead of n (fragment 0, and F = 1, keep
+    DiLoCo's steps).  With delay == 0 the fragment's engine is called; otherwise
+    it sends at that step and receives -- the merge -- `delay` steps later.
+
+    step(reps, local_step) is called on every step, after the inner optimizer.
+    finish() waits for the exchanges in flight and discards the merges still
+    pending: the parameters are left as the inner steps made them."""
+
+    def __init__(self, engines, bounds, H, delay=0):
+        self.engines, self.bounds = list(engines), [int(b) for b in bounds]
+        self.H, self.delay = int(H), int(delay)
+        F = len(self.engines)
+        if F < 1 or len(self.bounds) != F + 1:
+            raise ValueError(f"FragmentedOuter: {F} engines for {len(self.bounds)} bounds")
+        if not 0 <= self.delay < self.H:
+            raise ValueError(f"FragmentedOuter: delay={delay!r} is not in [0, H = {H})")
+        if self.delay and not all(hasattr(e, "send") and hasattr(e, "receive") for e in self.engines):
+            raise ValueError("FragmentedOuter: a delay needs engines with send / receive (DiLoCoOuterStream)")
+        self.due = [None] * F  # the step at which fragment f's pending merge lands
+        self.launch_elems = []  # of the last step() call
+        self.relocate_replicas = None  # accepted as on DiLoCoOuter; the set stays where it is
+        self.placement = {"placed": False, "why": "no search for a fragmented outer step", "fragments": F,
+                          "bounds": list(self.bounds)}
+
+    @property
+    def F(self):
+        return len(self.engines)
+
+    def fires(self, f, local_step):
+        return local_step > 0 and (local_step + (f * self.H) // self.F) % self.H == 0
+
+    def init_master(self, params_flat):
+        self.due = [None] * self.F
+        for f, eng in enumerate(self.engines):
+            eng.init_master(params_flat[self.bounds[f]:self.bounds[f + 1]])
+
+    def step(self, reps, local_step):
+        self.launch_elems = []
+        for f, eng in enumerate(self.engines):
+            view = reps[:, self.bounds[f]:self.bounds[f + 1]]
+            if self.due[f] is not None and self.due[f] <= local_step:
+                eng.receive(view)
+                self.due[f] = None
+                self.launch_elems += eng.launch_elems
+            if self.fires(f, local_step):
+                if self.delay == 0:
+                    eng(view)
+                    self.launch_elems += eng.launch_elems
+                else:
+                    eng.send(view)
+                    self.due[f] = local_step + self.delay
+
+    def finish(self):
+        for f, eng in enumerate(self.engines):
+            if self.due[f] is not None:
+                eng.cancel()
+                self.due[f] = None
 
 
 def sparta_capacity(n, p):

@@ -239,6 +239,35 @@ def diloco_outer_adam_masked(reps, bits, master, exp_avg, exp_avg_sq, n, sparse_
           "ga_diloco_outer_adam_masked")
 
 
+def diloco_outer_merge(src, master, mom, x, n, divisor, lr, momentum, dampening, weight_decay, nesterov, first_step,
+                       alpha):
+    """The streaming outer step's merge over [0, n) (ga_diloco_outer_merge): the SGD /
+    Nesterov outer update of the fp32 master / mom on the sum of src's rows over
+    divisor, then every row of x <- alpha * x + (1 - alpha) * master (alpha == 0: the
+    master, x not read).  x may be None (state update only) or src itself."""
+    src2 = _as2d(src)
+    x2 = _as2d(x) if x is not None else None
+    _gpu(src2, master, mom, x2)
+    K, lds = _rows_ld(src2)
+    Ko, ldx = _rows_ld(x2) if x2 is not None else (0, 0)
+    n = int(n)
+    if master.numel() < n or (mom is not None and mom.numel() < n) or src2.shape[1] < n:
+        raise ValueError("diloco_outer_merge: buffers shorter than n")
+    if x2 is not None and x2.shape[1] < n:
+        raise ValueError("diloco_outer_merge: x shorter than n")
+    if x2 is not None and x2.dtype != src2.dtype:
+        raise TypeError("diloco_outer_merge: src/x dtype mismatch")
+    for t in (master, mom):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError("diloco_outer_merge: master and momentum must be contiguous float32 tensors")
+    if not 0.0 <= float(alpha) < 1.0:
+        raise ValueError(f"diloco_outer_merge: alpha={alpha!r} is not in [0, 1)")
+    check(lib().ga_diloco_outer_merge(_dtype_code(src2), _p(src2), K, lds, n, float(divisor), _p(master), _p(mom),
+                                      int(bool(first_step)), float(lr), float(momentum), float(dampening),
+                                      float(weight_decay), int(bool(nesterov)), float(alpha), _p(x2), Ko, ldx,
+                                      _stream()), "ga_diloco_outer_merge")
+
+
 def quant_row_bytes(n, bits):
     """Bytes of one int8 / int4 payload row of n elements (ga_quant_row_bytes: 256-element
     blocks, q bytes then one fp32 scale per block, rounded up to 16)."""

@@ -48,10 +48,10 @@ from torch.utils.data import DataLoader
 from . import ops
 from .arena import ReplicaArena
 from .comm import Collective
-from .engine import DiLoCoOuter, DiLoCoOuterQuant, MeanReduce, demo_codec, node_mean
+from .engine import DiLoCoOuter, DiLoCoOuterQuant, FragmentedOuter, MeanReduce, demo_codec, node_mean
 from .fused_optim import build_fused
 from .strategy.demo import DeMoStrategy
-from .strategy.diloco import DiLoCoStrategy, build_outer_engine
+from .strategy.diloco import DiLoCoStrategy, build_outer_engine, build_streaming_outer, streaming_options
 from .strategy.federated_averaging import FedAvgStrategy
 from .strategy.sparta import SparseAverage, SPARTAStrategy
 from .strategy.sparta_diloco import SPARTADiLoCoStrategy
@@ -156,7 +156,13 @@ class ReplicaRunner:
             if isinstance(s, (DiLoCoStrategy, SPARTADiLoCoStrategy)):
                 # the fused kernel, or torch's optimizer on an fp32 master of node 0's start
                 # (diloco.py:26-28, 81-89) for any other outer OptimSpec
-                self.outer = build_outer_engine(s, s.outer_optim_spec, self.coll, self.K, ld, dev, dt)
+                # (a FragmentedOuter with DiLoCoStrategy's streaming options: asked on every step)
+                opts = streaming_options(s, s.outer_optim_spec)
+                if opts is not None:
+                    self.outer = build_streaming_outer(s, s.outer_optim_spec, self.coll, self.K, ld, dev, dt,
+                                                       self.ra.layout.offsets, opts)
+                else:
+                    self.outer = build_outer_engine(s, s.outer_optim_spec, self.coll, self.K, ld, dev, dt)
                 self.outer.init_master(self.ra.flat_set[0])
                 self.outer_optimizer = getattr(self.outer, "optimizer", None)
                 # the step may move the replica set itself (every model re-pointed)
@@ -213,7 +219,9 @@ class ReplicaRunner:
             self.optim.step(max_norm=self.max_norm)
         elif isinstance(s, DiLoCoStrategy):
             self.optim.step(max_norm=self.max_norm)
-            if s.local_step % s.H == 0 and s.local_step > 0:
+            if isinstance(self.outer, FragmentedOuter):
+                self.outer.step(P, s.local_step)
+            elif s.local_step % s.H == 0 and s.local_step > 0:
                 self.outer(P)
         elif isinstance(s, SPARTAStrategy):
             self.optim.step(max_norm=self.max_norm)
@@ -243,6 +251,12 @@ class ReplicaRunner:
             for cb in s.lr_callbacks:
                 cb(self.lr_scheds[0].get_last_lr()[0])
         s.local_step += 1
+
+    def finish(self):
+        """End of training: a streaming outer step's exchanges in flight are waited
+        for and its pending merges discarded (FragmentedOuter.finish)."""
+        if isinstance(getattr(self, "outer", None), FragmentedOuter):
+            self.outer.finish()
 
     def _place_demo(self, P, G, lr):
         """Once, after the first DeMo step: the K nodes' parameter, gradient and
@@ -665,6 +679,7 @@ class ReplicaTrainNode:
                 dist.barrier()
         if hasattr(self.runner, "sparta"):
             self.runner.sparta.check()
+        self.runner.finish()
         self._evaluate()
         return [m.state_dict() for m in self.models]
 

@@ -264,6 +264,31 @@ GA_API int ga_diloco_outer_adam_masked(int dtype, void* src, int64_t K, int64_t 
                                        float l2_wd, float step_size, float bc2_sqrt, void* dst,
                                        int64_t K_out, int64_t ld_dst, hipStream_t stream);
 
+/*
+ * The delayed, mixed merge of the streaming outer step (Streaming DiLoCo): the SGD /
+ * Nesterov outer update on a staged sum (or on the live rows), then every live row
+ * blended with the new master instead of overwritten.  Per element i, every line one
+ * individually rounded fp32 operation:
+ *   sum = 0.f + src_0[i] + ... + src_{K-1}[i]            (ascending k)
+ *   m   = ga_diloco_outer's update of (sum, master[i], mom[i]): avg = sum / divisor,
+ *         g = master[i] - avg, and its lines from there on, with the same fmaf's
+ *   master[i] = m;  mom[i] = buf                          (momentum != 0)
+ *   alpha == 0:  x_j[i] = T(m)                            x is not read
+ *   otherwise:   x_j[i] = T(fmaf(alpha, float(x_j[i]), (1.f - alpha) * m))   for j < K_out
+ * T is `dtype` (GA_F32 / GA_BF16, of src and x); master and mom are fp32, mom may be
+ * null when momentum == 0.  K_out may be 0 (state update only).  x may alias src when
+ * it is the same set (same base, K_out == K, ld_x == ld_src: the in-place one-process
+ * step): every source of an element is read before any store to it, and x_j[i] is read
+ * before it is written and never after.  alpha outside [0, 1) is GA_EINVAL; the other
+ * argument checks are ga_diloco_outer's.  With alpha == 0 the result is bit-identical to
+ * ga_diloco_outer with an fp32 master.  Algorithmic bytes per element (fp32): 4 K + 16
+ * (8 without momentum) + 4 K_out, or 8 K_out when alpha != 0.
+ */
+GA_API int ga_diloco_outer_merge(int dtype, const void* src, int64_t K, int64_t ld_src, int64_t n, float divisor,
+                                 float* master, float* mom, int first_step, float lr, float momentum,
+                                 float dampening, float weight_decay, int nesterov, float alpha,
+                                 void* x, int64_t K_out, int64_t ld_x, hipStream_t stream);
+
 /* ---- DiLoCo outer step on int8 / int4 block-quantised pseudo-gradients --- */
 
 /*
