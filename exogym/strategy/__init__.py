@@ -6,8 +6,8 @@ import *` raises AttributeError there; here the name resolves, and
 DiLoCoCommunicator (the name its module fails to import) is exported beside it.
 """
 from gym_amd.strategy import (CommunicateOptimizeStrategy, DeMoStrategy, DiLoCoCommunicator, DiLoCoStrategy,
-                              FedAvgStrategy, OptimSpec, SimpleReduceStrategy, SPARTADiLoCoStrategy, SPARTAStrategy,
-                              Strategy)
+                              FedAvgStrategy, IslandDiLoCoCommunicator, IslandDiLoCoStrategy, OptimSpec,
+                              SimpleReduceStrategy, SPARTADiLoCoStrategy, SPARTAStrategy, Strategy)
 
 __all__ = [
     "Strategy",
@@ -19,4 +19,6 @@ __all__ = [
     "DeMoStrategy",
     "SPARTADiLoCoStrategy",
     "DiLoCoCommunicator",
+    "IslandDiLoCoStrategy",
+    "IslandDiLoCoCommunicator",
 ]

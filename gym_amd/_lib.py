@@ -75,6 +75,8 @@ SIGNATURES = {
                                             c_i64, c_p]),
     "ga_diloco_outer_merge": (c_i32, [c_i32, c_p, c_i64, c_i64, c_i64, c_f32, c_p, c_p, c_i32, c_f32, c_f32, c_f32,
                                       c_f32, c_i32, c_f32, c_p, c_i64, c_i64, c_p]),
+    "ga_diloco_outer_islands": (c_i32, [c_i32, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64,
+                                        c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_p, c_i64, c_p]),
     "ga_quant_row_bytes": (c_i64, [c_i64, c_i32]),
     "ga_quant_encode": (c_i32, [c_i32, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_p]),
     "ga_diloco_outer_dequant": (c_i32, [c_p, c_i64, c_i64, c_i32, c_i64, c_f32, c_p, c_p, c_i32, c_f32, c_f32,

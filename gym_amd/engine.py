@@ -12,6 +12,7 @@ node count is K_total = world * K_local.
   DiLoCoOuterAdam  the same with an Adam/AdamW update  diloco.py:26-28
   DiLoCoOuterQuant  the SGD outer step on int8 / int4 block-quantised pseudo-gradients
   DiLoCoOuterStream  the SGD outer step sent at one step, merged `delay` steps later and mixed into the rows
+  DiLoCoOuterIslands  the SGD outer step per node against its island's average, per-node master and momentum
   FragmentedOuter  Streaming DiLoCo's schedule: one outer engine per fragment of the arena (fragment_bounds)
   TorchOuter   any other outer optimizer: torch's, on an fp32 master
   Sparta       sparse average (Philox or mask)      sparta.py:24-44
@@ -672,6 +673,53 @@ class DiLoCoOuterStream:
                              "after the other")
         self.send(reps)
         self.receive(reps)
+
+
+class DiLoCoOuterIslands:
+    """The island outer step (SGD family): every local node takes DiLoCo's outer
+    update against the average of its island, on a master and a momentum row of its
+    own (ga_diloco_outer_islands).
+
+    The caller draws the islands and brings their rows together (FedAvg's draw and
+    gather: strategy.island_diloco, replica.ReplicaRunner); a call makes ONE launch
+    for the round over exactly the islands that have a local member:
+        engine(src, islands, slots, x)
+    src [S, >= n] holds the gathered rows, islands[j] the ascending rows of island j,
+    slots[j][i] the local row (of master, momentum and x) of member islands[j][i] or
+    -1 for a member hosted by another process, x [K_local, >= n] the local nodes'
+    live rows (src itself for the in-place step of one process).
+
+    Master and momentum are fp32 and live PER NODE, [K_local, n] each (8 B per
+    parameter and node; DiLoCoOuter keeps one sharded copy for all nodes).  All nodes
+    take every round, so `first` is one flag.  No placement search, no masked (SPARTA
+    boundary) step, no exchange of its own (`coll` is kept for the record only)."""
+
+    def __init__(self, coll: Collective, K_local, n, device, dtype, lr=0.7, momentum=0.9, nesterov=True,
+                 dampening=0.0, weight_decay=0.0):
+        self.coll, self.K_local, self.n, self.dtype = coll, int(K_local), int(n), dtype
+        self.hp = dict(lr=lr, momentum=momentum, nesterov=nesterov, dampening=dampening, weight_decay=weight_decay)
+        self.master = torch.zeros(self.K_local, self.n, device=device, dtype=torch.float32)
+        self.mom = (torch.zeros(self.K_local, self.n, device=device, dtype=torch.float32)
+                    if momentum != 0 else None)
+        self.placement = {"placed": False, "why": "no search for the island outer step"}
+        self.first = True
+        self.launch_elems = []  # elements per row of each ga_diloco_outer_islands launch of the last round
+
+    def init_master(self, params_flat):
+        """Every node's master <- node 0's initial parameters (diloco.py:81-82)."""
+        self.master.copy_(params_flat[:self.n].to(torch.float32).expand(self.K_local, self.n))
+        self.first = True
+
+    def __call__(self, src, islands, slots, x):
+        local = [(list(isl), list(sl)) for isl, sl in zip(islands, slots) if any(v >= 0 for v in sl)]
+        if not local:
+            raise ValueError("DiLoCoOuterIslands: no island has a local member")
+        n, h = self.n, self.hp
+        ops.diloco_outer_islands(src[:, :n], [i for i, _ in local], [s for _, s in local], self.master, self.mom,
+                                 x[:, :n], n, h["lr"], h["momentum"], h["dampening"], h["weight_decay"],
+                                 h["nesterov"], self.first)
+        self.launch_elems = [n]
+        self.first = False
 
 
 def fragment_bounds(offsets, n, F, unit):

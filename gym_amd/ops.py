@@ -268,6 +268,82 @@ def diloco_outer_merge(src, master, mom, x, n, divisor, lr, momentum, dampening,
                                       _stream()), "ga_diloco_outer_merge")
 
 
+def island_table(islands, slots, S, K_state):
+    """The packed host table [starts | members | slots] of ga_diloco_outer_islands as a
+    list of ints, after the checks the kernel cannot make on device arrays: no empty
+    island, members ascending and in [0, S), every slot -1 or in [0, K_state) and used
+    at most once, at least one slot >= 0."""
+    islands = [[int(m) for m in isl] for isl in islands]
+    slots = [[int(v) for v in sl] for sl in slots]
+    if not islands or len(islands) != len(slots):
+        raise ValueError(f"diloco_outer_islands: {len(islands)} islands with {len(slots)} slot lists")
+    starts, used = [0], set()
+    for j, (isl, sl) in enumerate(zip(islands, slots)):
+        if not isl:
+            raise ValueError(f"diloco_outer_islands: island {j} is empty")
+        if len(sl) != len(isl):
+            raise ValueError(f"diloco_outer_islands: island {j} has {len(isl)} members and {len(sl)} slots")
+        if any(b <= a for a, b in zip(isl, isl[1:])):
+            raise ValueError(f"diloco_outer_islands: the members of island {j} are not ascending: {isl}")
+        if isl[0] < 0 or isl[-1] >= S:
+            raise ValueError(f"diloco_outer_islands: island {j} names a row outside [0, {S}): {isl}")
+        for v in sl:
+            if v == -1:
+                continue
+            if not 0 <= v < K_state:
+                raise ValueError(f"diloco_outer_islands: slot {v} of island {j} is not -1 or in [0, {K_state})")
+            if v in used:
+                raise ValueError(f"diloco_outer_islands: slot {v} is used twice")
+            used.add(v)
+        starts.append(starts[-1] + len(isl))
+    if not used:
+        raise ValueError("diloco_outer_islands: no slot >= 0 (nothing to update)")
+    return starts + [m for isl in islands for m in isl] + [v for sl in slots for v in sl]
+
+
+def diloco_outer_islands(src, islands, slots, master, mom, x, n, lr, momentum, dampening, weight_decay, nesterov,
+                         first_step):
+    """The island outer step over [0, n) (ga_diloco_outer_islands), one launch: for every
+    island (an ascending list of rows of src) the ascending fp32 sum of its rows, then
+    for every member with a slot >= 0 the SGD / Nesterov outer update of master[slot] /
+    mom[slot] against that sum over the island's size, and x[slot] <- master[slot].
+    islands and slots are host lists of lists (slots[j][i]: the row of master, mom and x
+    of member islands[j][i], -1 for a member that is summed only); they are validated
+    here and uploaded as one int32 tensor.  x may be src itself (in place)."""
+    src2, x2 = _as2d(src), _as2d(x)
+    m2 = _as2d(master)
+    b2 = _as2d(mom) if mom is not None else None
+    n = int(n)
+    S, lds = _rows_ld(src2)
+    K_state, ldx = _rows_ld(x2)
+    table = island_table(islands, slots, S, K_state)  # the host tables first: they need no GPU to be wrong
+    _gpu(src2, x2, m2, b2)
+    if x2.dtype != src2.dtype:
+        raise TypeError("diloco_outer_islands: src/x dtype mismatch")
+    for t in (m2, b2):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("diloco_outer_islands: master and momentum must be float32")
+        if t is not None and t.shape[0] != K_state:
+            raise ValueError(f"diloco_outer_islands: {t.shape[0]} state rows for {K_state} rows of x")
+    Km, ldm = _rows_ld(m2)
+    if b2 is not None and _rows_ld(b2) != (Km, ldm) and K_state > 1:
+        raise ValueError("diloco_outer_islands: master and momentum must have the same row stride")
+    if float(momentum) != 0.0 and b2 is None:
+        raise ValueError("diloco_outer_islands: momentum != 0 needs a momentum buffer")
+    if n < 0 or src2.shape[1] < n or x2.shape[1] < n or m2.shape[1] < n or (b2 is not None and b2.shape[1] < n):
+        raise ValueError("diloco_outer_islands: buffers shorter than n")
+    if any(t is not None and t.stride(1) != 1 for t in (src2, x2, m2, b2)):
+        raise ValueError("diloco_outer_islands: rows must be contiguous")
+    I = len(islands)
+    E = (len(table) - I - 1) // 2
+    dev_table = torch.tensor(table, dtype=torch.int32).to(src2.device, non_blocking=True)
+    starts, members, slot_t = dev_table[:I + 1], dev_table[I + 1:I + 1 + E], dev_table[I + 1 + E:]
+    check(lib().ga_diloco_outer_islands(_dtype_code(src2), _p(src2), S, lds, n, _p(starts), I, _p(members),
+                                        _p(slot_t), _p(m2), _p(b2), K_state, ldm, int(bool(first_step)), float(lr),
+                                        float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)),
+                                        _p(x2), ldx, _stream()), "ga_diloco_outer_islands")
+
+
 def quant_row_bytes(n, bits):
     """Bytes of one int8 / int4 payload row of n elements (ga_quant_row_bytes: 256-element
     blocks, q bytes then one fp32 scale per block, rounded up to 16)."""

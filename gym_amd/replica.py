@@ -16,7 +16,8 @@ minibatch_size`, its own clip_grad_norm_, then the strategy step.  Supported
 strategies: SimpleReduce, DiLoCo (any outer optimizer: the fused kernel for
 SGD, Adam and AdamW, torch's optimizer on an fp32 master otherwise), SPARTA (every
 selector: the torch-drawn masks of node 0 -- the reference uses rank 0's --
-or the Philox stream), FedAvg (full or island averaging), DeMo, SPARTA+DiLoCo (SPARTA's
+or the Philox stream), FedAvg (full or island averaging), Island DiLoCo (one
+ga_diloco_outer_islands launch per round for all local nodes), DeMo, SPARTA+DiLoCo (SPARTA's
 average and DiLoCo's outer step as above; in one process a step where both fire is
 one pass, ga_diloco_outer_masked).  Anything else runs on the process-per-node path
 (ReplicaRunner.supports).
@@ -48,11 +49,13 @@ from torch.utils.data import DataLoader
 from . import ops
 from .arena import ReplicaArena
 from .comm import Collective
-from .engine import DiLoCoOuter, DiLoCoOuterQuant, FragmentedOuter, MeanReduce, demo_codec, node_mean
+from .engine import (DiLoCoOuter, DiLoCoOuterIslands, DiLoCoOuterQuant, FragmentedOuter, MeanReduce, demo_codec,
+                     node_mean)
 from .fused_optim import build_fused
 from .strategy.demo import DeMoStrategy
 from .strategy.diloco import DiLoCoStrategy, build_outer_engine, build_streaming_outer, streaming_options
 from .strategy.federated_averaging import FedAvgStrategy
+from .strategy.island_diloco import IslandDiLoCoStrategy, check_island_options, draw_islands
 from .strategy.sparta import SparseAverage, SPARTAStrategy
 from .strategy.sparta_diloco import SPARTADiLoCoStrategy
 from .strategy.strategy import SimpleReduceStrategy, clip_and_step
@@ -101,7 +104,7 @@ class ReplicaRunner:
     def supports(strategy):
         if isinstance(strategy, (SPARTAStrategy, SPARTADiLoCoStrategy)):
             return True
-        if isinstance(strategy, FedAvgStrategy):
+        if isinstance(strategy, (FedAvgStrategy, IslandDiLoCoStrategy)):
             return True
         if isinstance(strategy, DiLoCoStrategy):
             return True  # any outer OptimSpec: fused kernel for SGD / Adam / AdamW, torch's optimizer otherwise
@@ -167,6 +170,13 @@ class ReplicaRunner:
                 self.outer_optimizer = getattr(self.outer, "optimizer", None)
                 # the step may move the replica set itself (every model re-pointed)
                 self.outer.relocate_replicas = self.ra.relocate_params
+            if isinstance(s, IslandDiLoCoStrategy):
+                # every local node's own fp32 master and momentum, started from node 0's parameters
+                hp = check_island_options(s.island_size, s.H, s.outer_optim_spec, s.kwargs)
+                self.outer = DiLoCoOuterIslands(self.coll, self.K, ld, dev, dt, **hp)
+                self.outer.init_master(self.ra.flat_set[0])
+                s.engine = self.outer  # Strategy.placement_records reads the outer step's record there
+                self._isl_all = None  # [num_nodes, ld]: every node's parameters, gathered (processes > 1)
             self.islands = (isinstance(s, FedAvgStrategy) and s.island_size is not None
                             and s.island_size < num_nodes)
             if isinstance(s, (SimpleReduceStrategy, FedAvgStrategy)) and not self.islands:
@@ -245,6 +255,10 @@ class ReplicaRunner:
                     self._island_average(P)
                 else:
                     self.mean(P)
+        elif isinstance(s, IslandDiLoCoStrategy):
+            self.optim.step(max_norm=self.max_norm)
+            if s.local_step % s.H == 0 and s.local_step > 0:
+                self._island_outer(P)
         for sch in self.lr_scheds:
             sch.step()
         if self.rank == 0 and self.lr_scheds:
@@ -291,20 +305,8 @@ class ReplicaRunner:
         through a row table, one launch per island), written to the members this
         process hosts.  With several processes each first all-gathers every
         node's parameters (the reference's all_gather), so islands may span them."""
-        N, s = self.num_nodes, self.s.island_size
-        ranks = list(range(N)) if self.rank == 0 else [None] * N
-        if self.rank == 0:
-            random.shuffle(ranks)
-        if self.coll.world > 1:
-            dist.broadcast_object_list(ranks, src=0)
-        src = P
-        if self.coll.exchange:
-            if self._isl_all is None:
-                self._isl_all = torch.empty(N, self.ra.ld, device=P.device, dtype=P.dtype)
-            self.coll.all_gather_into(self._isl_all.view(-1), P.reshape(-1))
-            src = self._isl_all
+        islands, src = self._draw_and_gather(P)
         lo, hi = self.first_node, self.first_node + self.K
-        islands = [sorted(ranks[i:i + s]) for i in range(0, N, s)]
         # every island's ascending member list in ONE host-to-device copy per round
         table = torch.tensor([m for isl in islands for m in isl], dtype=torch.int32).to(P.device, non_blocking=True)
         a = 0
@@ -318,6 +320,39 @@ class ReplicaRunner:
             # written back in one launch per run of consecutive member rows
             for a0, a1 in consecutive_runs(mine):
                 ops.replica_mean(self._isl_row, P[a0 - lo:a1 - lo + 1], divisor=1.0)
+
+    def _draw_and_gather(self, P):
+        """(this round's islands as ascending node lists, in the order of the draw; the
+        [num_nodes, ld] set their ids index): the first process shuffles the node ids
+        with Python's `random` and broadcasts them, the islands are consecutive slices
+        of island_size (None or >= num_nodes: one island of all nodes, no draw), and
+        with several processes every node's row is all-gathered."""
+        N, size = self.num_nodes, self.s.island_size
+        if size is None or size >= N:
+            ranks = list(range(N))
+        else:
+            ranks = list(range(N)) if self.rank == 0 else [None] * N
+            if self.rank == 0:
+                random.shuffle(ranks)
+            if self.coll.world > 1:
+                dist.broadcast_object_list(ranks, src=0)
+        src = P
+        if self.coll.exchange:
+            if self._isl_all is None:
+                self._isl_all = torch.empty(N, self.ra.ld, device=P.device, dtype=P.dtype)
+            self.coll.all_gather_into(self._isl_all.view(-1), P.reshape(-1))
+            src = self._isl_all
+        return draw_islands(ranks, size), src
+
+    def _island_outer(self, P):
+        """Island DiLoCo's round over the nodes of this process: _island_average's draw
+        and gather, then ONE ga_diloco_outer_islands launch over every island with a
+        local member -- each local member's own master and momentum stepped against
+        its island's ascending-node sum, its row overwritten with its master.  In one
+        process the rows are read and written in place."""
+        islands, src = self._draw_and_gather(P)
+        lo, hi = self.first_node, self.first_node + self.K
+        self.outer(src, islands, [[m - lo if lo <= m < hi else -1 for m in isl] for isl in islands], P)
 
     def averaged_flat(self):
         """The mean over all num_nodes nodes' parameters (a new [ld] buffer)."""

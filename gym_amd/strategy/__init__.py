@@ -9,6 +9,7 @@ from .communicate_optimize_strategy import CommunicateOptimizeStrategy, Communic
 from .demo import DeMoStrategy
 from .diloco import DiLoCoCommunicator, DiLoCoStrategy
 from .federated_averaging import FedAvgStrategy
+from .island_diloco import IslandDiLoCoCommunicator, IslandDiLoCoStrategy
 from .optim import OptimSpec, ensure_optim_spec
 from .sparta import SPARTAStrategy
 from .sparta_diloco import SPARTADiLoCoStrategy
@@ -25,4 +26,6 @@ __all__ = [
     "DeMoStrategy",
     "SPARTADiLoCoStrategy",
     "DiLoCoCommunicator",
+    "IslandDiLoCoStrategy",
+    "IslandDiLoCoCommunicator",
 ]

@@ -97,6 +97,30 @@ class AveragingCommunicator(CommunicationModule):
         key = tuple(sorted(members))
         return True, (self._groups[key][1] if len(key) > 1 else None)
 
+    def _gather_island(self, island_members: Set[int], num_nodes: int):
+        """The arenas of this rank's island brought together: (rows [R, n], the
+        ascending row indices of the island's members in it, whether those are all R
+        rows).  Over the island's sub-communicator every gathered row is a member, in
+        ascending rank order, and an island of one is the rank's own arena, not
+        gathered; on the world all-gather path every rank joins, islands of one too,
+        and the members are their ranks' rows."""
+        s = self.strategy
+        a = s.arena
+        members = sorted(island_members)
+        sub, coll = (self._island_collective(island_members, num_nodes)
+                     if s.coll.group is None and self._islands else (False, None))
+        if sub and len(members) == 1:
+            return a.flat.view(1, -1), [0], True
+        if sub:
+            rows_all, idx = len(members), list(range(len(members)))
+        else:
+            coll, rows_all, idx = s.coll, s.coll.world, members
+        if self._gathered is None or self._gathered.shape[0] < rows_all:
+            self._gathered = torch.empty(rows_all, a.n, device=a.device, dtype=a.dtype)
+        buf = self._gathered[:rows_all]
+        coll.all_gather_into(buf.view(-1), a.flat)
+        return buf, idx, sub
+
     def _average_models(self, model, island_members: Set[int], num_nodes: int) -> None:
         s = self.strategy
         a = s.arena
@@ -106,22 +130,9 @@ class AveragingCommunicator(CommunicationModule):
                 self._mean = MeanReduce(s.coll, 1, a.n, a.device, a.dtype)
             self._mean(a.flat.view(1, -1))
             return
-        members = sorted(island_members)
-        sub, coll = (self._island_collective(island_members, num_nodes)
-                     if s.coll.group is None and self._islands else (False, None))
-        if sub and len(members) == 1:  # (0 + x) / 1, as the reference's sum([x]) / 1
-            ops.replica_mean(a.flat.view(1, -1), a.flat, n=a.n)
-            return
-        if sub:
-            rows_all = len(members)
-            rows = None  # every gathered row is a member, in ascending rank order
-        else:  # every rank joins the world all-gather, islands of one too
-            coll, rows_all = s.coll, s.coll.world
-            rows = torch.tensor(members, dtype=torch.int32, device=a.device)
-        if self._gathered is None or self._gathered.shape[0] < rows_all:
-            self._gathered = torch.empty(rows_all, a.n, device=a.device, dtype=a.dtype)
-        buf = self._gathered[:rows_all]
-        coll.all_gather_into(buf.view(-1), a.flat)
+        buf, idx, every_row = self._gather_island(island_members, num_nodes)
+        # an island of one: (0 + x) / 1, as the reference's sum([x]) / 1
+        rows = None if every_row else torch.tensor(idx, dtype=torch.int32, device=a.device)
         ops.replica_mean(buf, a.flat, n=a.n, rows=rows)
 
     def communicate(self, model, rank: int, num_nodes: int, local_step: int) -> None:

@@ -289,6 +289,50 @@ GA_API int ga_diloco_outer_merge(int dtype, const void* src, int64_t K, int64_t 
                                  float dampening, float weight_decay, int nesterov, float alpha,
                                  void* x, int64_t K_out, int64_t ld_x, hipStream_t stream);
 
+/*
+ * The island outer step (no reference counterpart: the reference's outer step averages
+ * the world, diloco.py:34-37): every node takes ga_diloco_outer's SGD / Nesterov update
+ * against the average of its island, on a master and a momentum row of its own, all
+ * islands in one pass.  src holds S rows of `dtype` (GA_F32 / GA_BF16).  starts,
+ * members and slots are DEVICE int32 arrays: starts[0..I] delimits island j's entries
+ * in members and slots; members[e] is a source row in [0, S), ascending within an
+ * island; slots[e] is the row in [0, K_state) of that member's master, momentum and x,
+ * or -1 for a member hosted elsewhere, which is summed and not updated.  For island j
+ * with entries e0 = starts[j] .. e1 = starts[j + 1], per element i, every line one
+ * individually rounded fp32 operation:
+ *   sum = 0.f + src_{members[e0]}[i] + ... + src_{members[e1-1]}[i]     (ascending e)
+ *   for every entry e with slot = slots[e] >= 0:
+ *     m = ga_diloco_outer's update of (sum, divisor = float(e1 - e0), master_slot[i],
+ *         mom_slot[i]): avg = sum / divisor, g = master_slot[i] - avg, and its lines
+ *         from there on (weight decay, first step, momentum, dampening, Nesterov,
+ *         master -= lr * g), with the same fmaf's
+ *     master_slot[i] = m;  mom_slot[i] = buf                (momentum != 0)
+ *     x_slot[i] = T(m)
+ * master and mom are fp32 [K_state, ld_state], mom may be null when momentum == 0; x is
+ * [K_state, ld_x] of `dtype`.  first_step is one flag for the launch.  Rows of master,
+ * mom and x that no slot names are not touched, nor is anything past n in a row.
+ * The caller's contract, which the host cannot check on device tables and the kernel
+ * does not: every index is in range, every slot appears at most once, no island is
+ * empty.  x may alias src (the in-place step, slot == member row): a thread reads every
+ * member of its (island, vector) before it stores any, the stores of a vector go to
+ * rows of that island only, and no two threads share a vector of a row.  The vector
+ * path (16 B per lane, 8 B for bf16) runs when n % 4 == 0, the bases are so aligned and
+ * the lds are multiples of 4; otherwise an element path runs the same arithmetic.
+ * GA_EINVAL: n < 0, S < 1, K_state < 1, I < 1 or I > 65535 (the island is a grid
+ * dimension); a null src, master, x or table, or a null mom with momentum != 0; ld_src
+ * < n with S > 1; ld_x or ld_state < n with K_state > 1; master or mom not 4-byte
+ * aligned; Nesterov without a momentum or with dampening; an unknown dtype.  n == 0 is
+ * a no-op.  Algorithmic bytes per element of an island of s members of which L are
+ * local, fp32: 4 s + (16 + 4) L, or (8 + 4) L without momentum; with every member
+ * local that is 24 per node and element.
+ */
+GA_API int ga_diloco_outer_islands(int dtype, const void* src, int64_t S, int64_t ld_src, int64_t n,
+                                   const int32_t* starts, int64_t I, const int32_t* members,
+                                   const int32_t* slots, float* master, float* mom, int64_t K_state,
+                                   int64_t ld_state, int first_step, float lr, float momentum,
+                                   float dampening, float weight_decay, int nesterov, void* x, int64_t ld_x,
+                                   hipStream_t stream);
+
 /* ---- DiLoCo outer step on int8 / int4 block-quantised pseudo-gradients --- */
 
 /*
