@@ -11,6 +11,7 @@ node count is K_total = world * K_local.
   DiLoCoOuter  fused outer SGD/Nesterov step        diloco.py:34-76
   DiLoCoOuterAdam  the same with an Adam/AdamW update  diloco.py:26-28
   DiLoCoOuterQuant  the SGD outer step on int8 / int4 block-quantised pseudo-gradients
+  DiLoCoOuterTopK  the SGD outer step on top-k sparse pseudo-gradients (k per 4096-element chunk, error feedback)
   DiLoCoOuterStream  the SGD outer step sent at one step, merged `delay` steps later and mixed into the rows
   DiLoCoOuterIslands  the SGD outer step per node against its island's average, per-node master and momentum
   FragmentedOuter  Streaming DiLoCo's schedule: one outer engine per fragment of the arena (fragment_bounds)
@@ -589,6 +590,81 @@ class DiLoCoOuterQuant:
             self.coll.all_gather_into(self.payload.view(-1), own.view(-1))
         ops.diloco_outer_dequant(self.payload, self.master, self.mom, reps[:, :n], n, self.bits, self.K_total,
                                  h["lr"], h["momentum"], h["dampening"], h["weight_decay"], h["nesterov"], self.first)
+        self.launch_elems = [n]
+        self.first = False
+
+
+TOPK_MAX = 256  # entries per 4096-element chunk, ga_topk_encode's limit
+
+
+def check_topk(k):
+    """k of outer_topk as an int; ValueError unless it is an integer in 1..TOPK_MAX."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= TOPK_MAX:
+        raise ValueError(f"outer_topk={k!r}: expected an integer with 1 <= outer_topk <= {TOPK_MAX}")
+    return int(k)
+
+
+def topk_row_bytes(n, k):
+    """ga_topk_row_bytes on the host: k fp32 values and k uint16 indices per 4096-element
+    chunk, rounded up to 16 (no library call: the engine is built before any kernel runs)."""
+    return (-(-int(n) // 4096) * check_topk(k) * 6 + 15) // 16 * 16
+
+
+class DiLoCoOuterTopK:
+    """DiLoCo's outer step (SGD family) on top-k sparse pseudo-gradients, with
+    DiLoCoOuterQuant's call surface and state.
+
+    Every node sends the k largest-magnitude entries of each 4096-element chunk of
+    its pseudo-gradient master - x_k as (fp32 value, uint16 index) pairs
+    (ga_topk_encode), the payload rows are all-gathered in node order, and one
+    launch per process adds the K_total rows' entries in ascending node order,
+    divides by K_total and takes the outer update on EVERY element
+    (ga_diloco_outer_sparse), so all nodes end bit-identical without a broadcast.
+
+    Master and momentum are fp32 and REPLICATED on every process, not sharded (8 B
+    per parameter per rank).  error_feedback keeps a [K_local, n] fp32 residual:
+    what a node did not send is added to its next pseudo-gradient; without it the
+    unsent mass is dropped, so feedback is the intended use.  No placement search
+    and no masked (SPARTA boundary) step."""
+
+    def __init__(self, coll: Collective, K_local, n, device, dtype, k=32, error_feedback=False, lr=0.7,
+                 momentum=0.9, nesterov=True, dampening=0.0, weight_decay=0.0, placement=True):
+        self.k = check_topk(k)
+        self.coll, self.K_local, self.n = coll, int(K_local), int(n)
+        self.K_total = coll.world * self.K_local
+        self.hp = dict(lr=lr, momentum=momentum, nesterov=nesterov, dampening=dampening, weight_decay=weight_decay)
+        self.shard, self.per, self.dtype = False, self.n, dtype
+        self._state = torch.zeros((2 if momentum != 0 else 1) * self.n, device=device, dtype=torch.float32)
+        self.master = self._state[:self.n]
+        self.mom = self._state[self.n:] if momentum != 0 else None
+        self.residual = (torch.zeros(self.K_local, self.n, device=device, dtype=torch.float32)
+                         if error_feedback else None)
+        self.payload_bytes_per_node = topk_row_bytes(self.n, self.k)
+        self.payload = torch.zeros(self.K_total, self.payload_bytes_per_node, device=device, dtype=torch.uint8)
+        self.placement = {"placed": False, "why": "no search for the sparse outer step"}
+        self.relocate_replicas = None  # accepted as on DiLoCoOuter; the set stays where it is
+        self.first = True
+        self.launch_elems = []  # elements per ga_diloco_outer_sparse launch of the last step
+
+    def init_master(self, params_flat):
+        """master <- the node's initial parameters (diloco.py:81-82); no error carried over."""
+        self.master.copy_(params_flat[:self.n])
+        if self.residual is not None:
+            self.residual.zero_()
+        self.first = True
+
+    def __call__(self, reps, sparse_mask=None):
+        if sparse_mask is not None:
+            raise ValueError("DiLoCoOuterTopK: no one-pass masked outer step; run Sparta and the outer step one "
+                             "after the other")
+        n, K, h = self.n, self.K_local, self.hp
+        a = self.coll.rank * K
+        own = self.payload[a:a + K]
+        ops.topk_encode(reps[:, :n], self.master, self.residual, own, n, self.k)
+        if self.coll.exchange:
+            self.coll.all_gather_into(self.payload.view(-1), own.view(-1))
+        ops.diloco_outer_sparse(self.payload, self.master, self.mom, reps[:, :n], n, self.k, self.K_total,
+                                h["lr"], h["momentum"], h["dampening"], h["weight_decay"], h["nesterov"], self.first)
         self.launch_elems = [n]
         self.first = False
 

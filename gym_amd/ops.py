@@ -413,6 +413,78 @@ def diloco_outer_dequant(payload, master, mom, dst, n, bits, divisor, lr, moment
                                         _stream()), "ga_diloco_outer_dequant")
 
 
+def topk_row_bytes(n, k):
+    """Bytes of one top-k payload row of n elements (ga_topk_row_bytes: 4096-element chunks,
+    k fp32 values then k uint16 indices per chunk, rounded up to 16)."""
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise ValueError(f"topk_row_bytes: k={k!r} must be an integer in 1..256")
+    nbytes = int(lib().ga_topk_row_bytes(int(n), k))
+    if nbytes < 0:
+        raise ValueError(f"topk_row_bytes: n={n} must be >= 0 and k={k} in 1..256")
+    return nbytes
+
+
+def _topk_ld(who, payload, rows, n, k):
+    if payload.dtype != torch.uint8 or payload.dim() != 2 or payload.stride(1) != 1:
+        raise TypeError(f"{who}: the payload is a 2-D uint8 tensor with contiguous rows")
+    if payload.shape[0] != rows:
+        raise ValueError(f"{who}: {payload.shape[0]} payload rows for {rows} rows")
+    need = topk_row_bytes(n, k)
+    ld = payload.stride(0) if rows > 1 else max(payload.shape[1], need) // 16 * 16
+    if payload.shape[1] < need or ld < need:
+        raise ValueError(f"{who}: payload rows of {payload.shape[1]} bytes, {need} needed")
+    return ld
+
+
+def topk_encode(rows, master, residual, payload, n, k):
+    """payload[r] <- the k largest-magnitude entries of every 4096-element chunk of the
+    pseudo-gradient master - rows[r] (+ residual[r], which then keeps what was not sent)
+    of every row r of the replica set (ga_topk_encode; payload: uint8 [K, >=
+    topk_row_bytes(n, k)])."""
+    x2 = _as2d(rows)
+    r2 = _as2d(residual) if residual is not None else None
+    _gpu(x2, master, r2, payload)
+    K, ldx = _rows_ld(x2)
+    n = int(n)
+    if n < 0 or x2.shape[1] < n or master.numel() < n or (r2 is not None and r2.shape[1] < n):
+        raise ValueError("topk_encode: buffers shorter than n")
+    if master.dtype != torch.float32 or not master.is_contiguous():
+        raise TypeError("topk_encode: master must be a contiguous float32 tensor")
+    ldr = 0
+    if r2 is not None:
+        if r2.dtype != torch.float32 or r2.shape[0] != K:
+            raise TypeError("topk_encode: the residual is a float32 set with one row per row of x")
+        ldr = _rows_ld(r2)[1]
+    ldq = _topk_ld("topk_encode", payload, K, n, k)
+    check(lib().ga_topk_encode(_dtype_code(x2), _p(x2), K, ldx, _p(master), _p(r2), ldr, n, k, _p(payload), ldq,
+                               _stream()), "ga_topk_encode")
+
+
+def diloco_outer_sparse(payload, master, mom, dst_rows, n, k, divisor, lr, momentum, dampening, weight_decay,
+                        nesterov, first):
+    """The DiLoCo outer step on the sum of the S top-k payload rows over divisor
+    (ga_diloco_outer_sparse): master / mom (fp32) updated as by diloco_outer on every
+    element, every row of dst_rows <- the new master."""
+    dst2 = _as2d(dst_rows) if dst_rows is not None else None
+    _gpu(payload, master, mom, dst2)
+    n = int(n)
+    Ko, ldd = _rows_ld(dst2) if dst2 is not None else (0, 0)
+    if n < 0 or master.numel() < n or (mom is not None and mom.numel() < n):
+        raise ValueError("diloco_outer_sparse: buffers shorter than n")
+    if dst2 is not None and dst2.shape[1] < n:
+        raise ValueError("diloco_outer_sparse: dst shorter than n")
+    for t in (master, mom):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError("diloco_outer_sparse: master and momentum must be contiguous float32 tensors")
+    S = payload.shape[0] if payload.dim() == 2 else -1
+    ldq = _topk_ld("diloco_outer_sparse", payload, S, n, k)
+    code = _dtype_code(dst2) if dst2 is not None else _lib.GA_F32
+    check(lib().ga_diloco_outer_sparse(_p(payload), S, ldq, k, n, float(divisor), _p(master), _p(mom),
+                                       int(bool(first)), float(lr), float(momentum), float(dampening),
+                                       float(weight_decay), int(bool(nesterov)), code, _p(dst2), Ko, ldd,
+                                       _stream()), "ga_diloco_outer_sparse")
+
+
 def sparta_gap_table(p):
     """The 64-entry gap table of the Philox mask stream (include/gym_amd.h)."""
     import ctypes

@@ -25,6 +25,16 @@ all-gather of the payload rows, ga_diloco_outer_dequant), outer_error_feedback=T
 carries each node's quantisation error into its next outer step.  SGD-family outer
 optimizers only; the master and momentum are then replicated on every rank.
 
+outer_compression="topk" sends the outer_topk (default 32, 1..256) largest-magnitude
+entries of every 4096-element chunk of the pseudo-gradient as (fp32 value, uint16
+index) pairs (engine.DiLoCoOuterTopK: ga_topk_encode, one all-gather,
+ga_diloco_outer_sparse, which updates every element): nc * k * 6 bytes per node and
+outer step, 192 B per 4096 parameters at k = 32.  outer_error_feedback=True keeps what
+a node did not send for its next outer step; without it the unsent mass is dropped,
+so feedback is the intended use.  outer_topk is ignored for any other compression.
+Same restrictions as the quantised step (plain SGD outer optimizer, no delay / mix);
+it composes with num_fragments (chunks restart at each fragment's start).
+
 Streaming DiLoCo (DESIGN §3 "Streaming outer step"): num_fragments=F cuts the arena
 into F fragments that take their outer steps on staggered schedules (an outer event
 moves about n / F elements), outer_delay=tau applies an exchange's result tau inner
@@ -38,11 +48,14 @@ from typing import Optional, Union
 import torch
 
 from .. import ops
-from ..engine import (QUANT_BITS, DiLoCoOuter, DiLoCoOuterAdam, DiLoCoOuterQuant, DiLoCoOuterStream, FragmentedOuter,
-                      TorchOuter, fragment_bounds)
+from ..engine import (QUANT_BITS, DiLoCoOuter, DiLoCoOuterAdam, DiLoCoOuterQuant, DiLoCoOuterStream, DiLoCoOuterTopK,
+                      FragmentedOuter, TorchOuter, check_topk, fragment_bounds)
 from .communicate_optimize_strategy import CommunicationModule
 from .optim import OptimSpec, ensure_optim_spec
 from .strategy import Strategy, build_inner_optimizer, clip_and_step
+
+
+TOPK = "topk"  # outer_compression: the k largest entries per 4096-element chunk (outer_topk)
 
 
 def fused_sgd_hparams(spec: OptimSpec):
@@ -88,17 +101,23 @@ def fused_adam_hparams(spec: OptimSpec):
                 weight_decay=float(weight_decay), decoupled=decoupled)
 
 
-def check_outer_compression(compression, spec):
-    """The bit width of outer_compression (None: off) for outer OptimSpec `spec`;
-    ValueError for an unknown string or an outer optimizer without a quantised step."""
+def check_outer_compression(compression, spec, topk=32):
+    """The bit width of outer_compression (None: off; TOPK itself for "topk", after
+    outer_topk = `topk` was checked) for outer OptimSpec `spec`; ValueError for an
+    unknown string or an outer optimizer without a compressed step.  outer_topk is
+    not looked at for any other compression."""
     if compression is None:
         return None
-    if compression not in QUANT_BITS:
-        raise ValueError(f"outer_compression={compression!r}: expected None, " + " or ".join(map(repr, QUANT_BITS)))
+    if not isinstance(compression, str) or (compression != TOPK and compression not in QUANT_BITS):
+        raise ValueError(f"outer_compression={compression!r}: expected None, "
+                         + " or ".join(map(repr, [*QUANT_BITS, TOPK])))
     if fused_sgd_hparams(spec) is None:
         raise ValueError(f"outer_compression={compression!r} needs a plain torch.optim.SGD outer optimizer (the "
-                         f"quantised outer step has no other update); got {spec.cls.__name__} with "
+                         f"quantised and sparse outer steps have no other update); got {spec.cls.__name__} with "
                          f"{dict(spec.kwargs or {})}")
+    if compression == TOPK:
+        check_topk(topk)
+        return TOPK
     return QUANT_BITS[compression]
 
 
@@ -145,11 +164,17 @@ def build_outer_engine(strategy, spec, coll, K_local, n, device, dtype, placemen
     strategy was built with fused_outer=False (the A/B switch against torch's
     optimizer; SGD specs are always fused), TorchOuter (torch's optimizer on an
     fp32 master) for every other spec.  With outer_compression set:
-    DiLoCoOuterQuant for plain SGD, ValueError for anything else.  placement: the
-    engine's placement option, None for the strategy's."""
+    DiLoCoOuterQuant ("int8" / "int4") or DiLoCoOuterTopK ("topk", k = outer_topk)
+    for plain SGD, ValueError for anything else.  placement: the engine's placement
+    option, None for the strategy's."""
     placement = strategy.placement_opt if placement is None else placement
-    bits = check_outer_compression(strategy.kwargs.get("outer_compression"), spec)
+    bits = check_outer_compression(strategy.kwargs.get("outer_compression"), spec,
+                                   strategy.kwargs.get("outer_topk", 32))
     hp = fused_sgd_hparams(spec)
+    if bits == TOPK:
+        return DiLoCoOuterTopK(coll, K_local, n, device, dtype, k=strategy.kwargs.get("outer_topk", 32),
+                               placement=placement,
+                               error_feedback=bool(strategy.kwargs.get("outer_error_feedback", False)), **hp)
     if bits is not None:
         return DiLoCoOuterQuant(coll, K_local, n, device, dtype, bits=bits, placement=placement,
                                 error_feedback=bool(strategy.kwargs.get("outer_error_feedback", False)), **hp)
@@ -166,7 +191,7 @@ def build_streaming_outer(strategy, spec, coll, K_local, n, device, dtype, offse
     [K_local, n] set whose tensors start at `offsets`: the arena cut by
     engine.fragment_bounds in units of 512 * world elements, one engine per fragment
     -- DiLoCoOuterStream with a delay or a mix, otherwise whatever build_outer_engine
-    chooses for the spec (DiLoCoOuter, DiLoCoOuterAdam, DiLoCoOuterQuant), without a
+    chooses for the spec (DiLoCoOuter, DiLoCoOuterAdam, DiLoCoOuterQuant, DiLoCoOuterTopK), without a
     placement search and with n the fragment's length.  A spec that takes torch's
     optimizer (TorchOuter) has no fragments."""
     F, delay, mix = opts
@@ -239,16 +264,18 @@ class DiLoCoStrategy(Strategy):
     def __init__(self, optim_spec: Optional[Union[str, OptimSpec]] = None,
                  outer_optim_spec: Optional[Union[str, OptimSpec]] = None, H: int = 100,
                  outer_compression: Optional[str] = None, outer_error_feedback: bool = False,
-                 num_fragments: int = 1, outer_delay: int = 0, outer_mix: float = 0.0, **kwargs):
+                 num_fragments: int = 1, outer_delay: int = 0, outer_mix: float = 0.0, outer_topk: int = 32,
+                 **kwargs):
         self.inner_optim_spec = ensure_optim_spec(optim_spec, OptimSpec(torch.optim.AdamW))
         self.outer_optim_spec = ensure_optim_spec(outer_optim_spec, default_outer_spec())
         self.H = H
-        check_outer_compression(outer_compression, self.outer_optim_spec)
+        check_outer_compression(outer_compression, self.outer_optim_spec, outer_topk)
         num_fragments, outer_delay, outer_mix = check_streaming(num_fragments, outer_delay, outer_mix, H,
                                                                 self.outer_optim_spec, outer_compression)
         # all reach build_outer_engine / build_streaming_outer through self.kwargs, as fused_outer does
         super().__init__(outer_compression=outer_compression, outer_error_feedback=bool(outer_error_feedback),
-                         num_fragments=num_fragments, outer_delay=outer_delay, outer_mix=outer_mix, **kwargs)
+                         num_fragments=num_fragments, outer_delay=outer_delay, outer_mix=outer_mix,
+                         outer_topk=outer_topk, **kwargs)
 
     def _init_node(self, model, rank, num_nodes):
         super()._init_node(model, rank, num_nodes)

@@ -23,7 +23,9 @@ fuse_boundary reads False.
 outer_compression= / outer_error_feedback= as on DiLoCoStrategy (int8 / int4
 block-quantised pseudo-gradients, SGD-family outer optimizers).  The quantised
 outer step has no masked form: the two modules run in sequence and
-fuse_boundary reads False.
+fuse_boundary reads False.  outer_compression="topk" with outer_topk= (default 32)
+sends the k largest entries of every 4096-element chunk instead, with the same
+restrictions.
 """
 from typing import Optional, Union
 
@@ -37,14 +39,14 @@ class SPARTADiLoCoStrategy(CommunicateOptimizeStrategy):
     def __init__(self, inner_optim: Optional[Union[str, OptimSpec]] = None,
                  outer_optim: Optional[Union[str, OptimSpec]] = None, p_sparta: float = 0.005, H: int = 100,
                  mask_source="torch", fuse_boundary=True, outer_compression: Optional[str] = None,
-                 outer_error_feedback: bool = False, **kwargs):
+                 outer_error_feedback: bool = False, outer_topk: int = 32, **kwargs):
         index_selector = RandomIndexSelector(p_sparta, mask_source=mask_source)
         sparse_comm = SparseCommunicator(index_selector)
         diloco_comm = DiLoCoCommunicator(H=H, outer_optim=outer_optim)
-        check_outer_compression(outer_compression, diloco_comm.outer_optim_spec)
+        check_outer_compression(outer_compression, diloco_comm.outer_optim_spec, outer_topk)
         super().__init__(communication_modules=[sparse_comm, diloco_comm], inner_optim=inner_optim,
                          outer_compression=outer_compression, outer_error_feedback=bool(outer_error_feedback),
-                         **kwargs)
+                         outer_topk=outer_topk, **kwargs)
         self.index_selector = index_selector
         self.p_sparta = p_sparta
         self.H = H

@@ -388,6 +388,63 @@ GA_API int ga_diloco_outer_dequant(const void* payload, int64_t S, int64_t ld_q_
                                    float momentum, float dampening, float weight_decay, int nesterov, int dtype,
                                    void* dst, int64_t K_out, int64_t ld_dst, hipStream_t stream);
 
+/* ---- DiLoCo outer step on top-k sparse pseudo-gradients ----------------- */
+
+/*
+ * The sparse format, on the wire and in memory (no reference counterpart).  Chunks are
+ * 4096 consecutive elements of an arena row, nc = ceil(n / 4096), the last may be short
+ * (length L); k is the entries per chunk, 1 <= k <= 256.  One payload row per node, in
+ * bytes:
+ *   [ vals : nc * k x fp32 ][ idx : nc * k x uint16 ]
+ * Chunk c owns entries c*k .. c*k + k - 1 of both sections: min(k, L) real entries in
+ * ascending index order (idx = offset inside the chunk, 0..4095), the remaining ones
+ * val = +0.0f, idx = 0xFFFF (skipped by the decoder).  A chunk with fewer than k
+ * non-zeros still emits k entries.  The pad bytes are 0.
+ * ga_topk_row_bytes: that size rounded up to a multiple of 16 (host only; -1 for n < 0
+ * or k outside 1..256).
+ */
+GA_API int64_t ga_topk_row_bytes(int64_t n, int k);
+
+/*
+ * Encode the pseudo-gradients of K rows x [K, ld_x] (f32 / bf16) against an fp32
+ * master into K payload rows (row r at payload + r * ld_q_bytes).  Every line is one
+ * individually rounded fp32 operation:
+ *   d   = master[i] - float(x[r, i])
+ *   d   = d + residual[r, i]                   (residual != null: error feedback)
+ *   key = bits(d) & 0x7fffffff as an unsigned integer (a total order: infinities and
+ *         NaNs sort first)
+ *   selected: the first min(k, L) elements of the chunk ordered by (key descending,
+ *   index ascending) -- ties at the k-th magnitude go to the lowest indices
+ *   payload value = d bit for bit
+ *   residual[r, i] = d - d where selected, d elsewhere      (residual != null)
+ * residual is an fp32 [K, ld_r] set or null.  ld_q_bytes >= ga_topk_row_bytes(n, k)
+ * and a multiple of 16, payload 16-byte aligned; bytes of a payload row past its
+ * row_bytes are not written.  x / master / residual may have any element alignment
+ * and ld (16-byte vector access when aligned, element access otherwise, the same bytes
+ * either way); elements at or past n are never read or written.  Algorithmic bytes per
+ * element, fp32: 4 + K (4 + 6 k / 4096), + 8 K with a residual.
+ */
+GA_API int ga_topk_encode(int dtype, const void* x, int64_t K, int64_t ld_x, const float* master,
+                          float* residual, int64_t ld_r, int64_t n, int k, void* payload,
+                          int64_t ld_q_bytes, hipStream_t stream);
+
+/*
+ * Decode S payload rows (ga_topk_encode's format, row r at payload + r * ld_q_bytes,
+ * node order) and take the outer step, one pass over ALL n elements:
+ *   acc = +0; for r in 0..S-1, if row r's chunk lists i: acc = acc + val
+ *   g   = acc / divisor
+ *   ga_diloco_outer's update from its pseudo-gradient on (weight decay, first step,
+ *   momentum, dampening, Nesterov, master -= lr * g) on the fp32 master / mom
+ *   dst_j[i] = master[i] rounded to `dtype`  for j < K_out
+ * An entry whose idx is 0xFFFF (or any value >= 4096) is skipped.  S has no upper
+ * limit.  mom may be null when momentum == 0.  Algorithmic bytes per element:
+ * S * 6 k / 4096 + 16 (8 without momentum) + K_out * sizeof(dtype).
+ */
+GA_API int ga_diloco_outer_sparse(const void* payload, int64_t S, int64_t ld_q_bytes, int k, int64_t n,
+                                  float divisor, float* master, float* mom, int first_step, float lr,
+                                  float momentum, float dampening, float weight_decay, int nesterov, int dtype,
+                                  void* dst, int64_t K_out, int64_t ld_dst, hipStream_t stream);
+
 /* ---- SPARTA sparse averaging ------------------------------------------- */
 
 /* Workspace bytes needed by ga_sparta_select for an arena of n elements. */
