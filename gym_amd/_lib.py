@@ -96,6 +96,10 @@ SIGNATURES = {
     "ga_sparta_scatter": (c_i32, [c_i32, c_p, c_p, c_p, c_i64, c_f32, c_p, c_i64, c_i64, c_i32, c_p]),
     "ga_sparta_average_local": (c_i32, [c_i32, c_p, c_i64, c_i64, c_i32, c_i64, c_p, c_i32, c_u64, c_u64, c_f64, c_p,
                                         c_i64, c_f32, c_p, c_p, c_i64, c_p, c_p, c_p]),
+    "ga_sparta_average_listed": (c_i32, [c_i32, c_p, c_i64, c_i64, c_i32, c_i64, c_p, c_i64, c_p, c_i32, c_i64,
+                                         c_f32, c_p]),
+    "ga_sparta_gather_listed": (c_i32, [c_i32, c_p, c_i64, c_i64, c_i32, c_i64, c_p, c_i64, c_p, c_i32, c_i64, c_p,
+                                        c_p, c_p, c_p]),
     "ga_demo_tensor_bytes": (c_i32, []),
     "ga_demo_encode": (c_i32, [c_i32, c_p, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_f32, c_f32,
                                c_f32, c_p, c_i64, c_i64, c_p]),

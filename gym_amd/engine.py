@@ -952,6 +952,24 @@ class Sparta:
                 self._pending.clear()
                 raise RuntimeError(f"SPARTA: {int(hb[0])} elements selected > capacity {self.cap}")
 
+    def listed(self, reps, order, table, total):
+        """The step of a cycle selector from its index lists (strategy.sparta.
+        ListedPlan): `table` rows {start, count, prefix} into the int32 `order`
+        arena, `total` selected elements, known on the host.  No exchange: one
+        ga_sparta_average_listed launch.  With an exchange (`order` already rank
+        0's on every rank): gather, all-reduce of vals[:total], scatter; the
+        count is exact, so nothing is read back and no overflow flag is polled."""
+        if total == 0:
+            return
+        if not self.coll.exchange:
+            ops.sparta_average_listed(reps, order, table, total, float(self.K_total), n=self.n, layout=self.layout)
+            return
+        self._ensure_cap(total)
+        ops.sparta_gather_listed(reps, order, table, total, self.idx, self.vals, self.count, n=self.n,
+                                 layout=self.layout)
+        self.coll.all_reduce_(self.vals[:total])
+        ops.sparta_scatter(self.vals, self.idx, self.count, total, float(self.K_total), reps, layout=self.layout)
+
     def __call__(self, reps, seed=0, iteration=0, mask=None, skip=None, mask_cap=None, mask_shared=False):
         """mask: this process's uint8/bool mask arena (the reference selector's
         draws), or its packed int64 words, or None for the Philox stream.  With an exchange, rank 0's mask

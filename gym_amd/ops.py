@@ -688,6 +688,46 @@ def sparta_scatter(vals, idx, count, cap, divisor, dst, layout="rows"):
                                   _p(dst2), K, ld, code, _stream()), "ga_sparta_scatter")
 
 
+def _listed_args(who, reps, order, table, total, n, layout):
+    r2, K, ld, code = _sparta_set(reps, layout)
+    n = _rows_of(r2, code) if n is None else int(n)
+    if _rows_of(r2, code) < n:
+        raise ValueError(f"{who}: replica set shorter than n")
+    if order.dtype != torch.int32 or order.dim() != 1 or not order.is_contiguous():
+        raise ValueError(f"{who}: order must be a contiguous int32 vector")
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 3 or not table.is_contiguous():
+        raise ValueError(f"{who}: table must be a contiguous int32 [T, 3] tensor of {{start, count, prefix}} rows")
+    if not 0 <= int(total) <= order.numel():
+        raise ValueError(f"{who}: total={total} outside [0, {order.numel()}]")
+    return r2, K, ld, code, n
+
+
+def sparta_average_listed(reps, order, table, total, divisor, n=None, layout="rows"):
+    """SPARTA step from index lists (ga_sparta_average_listed): for every row
+    {start, count, prefix} of `table` the elements order[start:start + count] of
+    every replica <- (sum over replicas) / divisor; total = the sum of the counts."""
+    _gpu(reps, order, table)
+    r2, K, ld, code, n = _listed_args("sparta_average_listed", reps, order, table, total, n, layout)
+    check(lib().ga_sparta_average_listed(_dtype_code(r2), _p(r2), K, ld, code, n, _p(order), order.numel(), _p(table),
+                                         int(table.shape[0]), int(total), float(divisor), _stream()),
+          "ga_sparta_average_listed")
+
+
+def sparta_gather_listed(src, order, table, total, idx, vals, count, n=None, layout="rows"):
+    """The exchange path's gather over the same lists (ga_sparta_gather_listed):
+    idx[j] = the j-th listed element, vals[j] = its sum over the replicas of src,
+    count = {total, 0}; sparta_scatter follows the all-reduce of vals[:total]."""
+    _gpu(src, order, table, idx, vals, count)
+    s2, K, ld, code, n = _listed_args("sparta_gather_listed", src, order, table, total, n, layout)
+    if idx.dtype != torch.int32 or count.dtype != torch.int64 or count.numel() < 2 or vals.dtype != s2.dtype:
+        raise TypeError("sparta_gather_listed: idx int32, vals arena dtype, count int64[2]")
+    if idx.numel() < total or vals.numel() < total:
+        raise ValueError("sparta_gather_listed: idx/vals smaller than total")
+    check(lib().ga_sparta_gather_listed(_dtype_code(s2), _p(s2), K, ld, code, n, _p(order), order.numel(), _p(table),
+                                        int(table.shape[0]), int(total), _p(idx), _p(vals), _p(count), _stream()),
+          "ga_sparta_gather_listed")
+
+
 def _demo_dtype(plan, t):
     """The arena dtype code, or GA_BF16_REF for a bf16 arena under a plan with
     the reference's bf16 arithmetic (DemoPlan(bf16_transform="reference"))."""

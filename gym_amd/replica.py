@@ -194,9 +194,10 @@ class ReplicaRunner:
                 self.sparta.bind(s.index_selector, self.coll, self.K, self.ra.layout, ld, dev, dt)
             if isinstance(s, SPARTADiLoCoStrategy):
                 # a boundary step as one pass: needs the mask as packed words in memory, every node in
-                # this process, and the fused outer engine
-                self.fuse = bool(s.fuse_boundary and not self.sparta.philox and not self.coll.exchange
-                                 and isinstance(self.outer, DiLoCoOuter))
+                # this process, and the fused outer engine (a listed selector keeps no mask: its
+                # boundary step is the listed average, then the plain outer step)
+                self.fuse = bool(s.fuse_boundary and not self.sparta.philox and self.sparta.plan is None
+                                 and not self.coll.exchange and isinstance(self.outer, DiLoCoOuter))
                 s.fuse_boundary = self.fuse
                 if isinstance(self.outer, (DiLoCoOuter, DiLoCoOuterQuant, DiLoCoOuterTopK)):
                     s.engine = self.outer  # Strategy.placement_records reads the outer step's record there

@@ -30,7 +30,9 @@ mask_source=...)):
       Tensors without a gradient are skipped as in the reference (a skip-range
       table passed to the kernel).
 The ShuffledSequential / Partitioned selectors are the reference's algorithms
-(the same torch draws on the device) feeding the mask-mode kernels.
+(the same torch draws on the device) feeding the mask-mode kernels, or with
+listed=True on a GPU arena their index lists feeding ga_sparta_average_listed
+(ListedPlan: no mask, no count read back; the same selections and generator state).
 
 SparseAverage is the one copy of the per-step orchestration (shared seed, skip
 table, mask arena and draw state, the mask_cap rule, the iteration counter):
@@ -294,7 +296,13 @@ def _draw_fused(selector, params, views, skip, state, bits=None, coll=None, defe
 
 
 class ShuffledSequentialIndexSelector(IndexSelector):
-    """Cycles through a per-tensor random permutation in ceil(1/p) chunks."""
+    """Cycles through a per-tensor random permutation in ceil(1/p) chunks.
+    listed=True: on a GPU arena the step runs from index lists (ListedPlan)
+    instead of per-tensor masks; the same selections, the same generator calls."""
+
+    def __init__(self, p, listed=False):
+        super().__init__(p)
+        self.listed = bool(listed)
 
     def get_indices(self, param, iteration):
         n = param.numel()
@@ -318,7 +326,11 @@ class ShuffledSequentialIndexSelector(IndexSelector):
 
 class PartitionedIndexSelector(IndexSelector):
     """Random partition of each tensor into ceil(1/p) parts, visited in turn,
-    re-drawn when a cycle ends."""
+    re-drawn when a cycle ends.  listed=True: as on ShuffledSequentialIndexSelector."""
+
+    def __init__(self, p, listed=False):
+        super().__init__(p)
+        self.listed = bool(listed)
 
     def _set_partition(self, param):
         st = self.state[param]
@@ -346,6 +358,120 @@ class PartitionedIndexSelector(IndexSelector):
         return mask
 
 
+class ListedPlan:
+    """The selections of a cycle selector (ShuffledSequential / Partitioned) as
+    index lists for ga_sparta_average_listed, instead of a mask per step.
+
+    `order`: one int32 arena of n entries; at tensor i's arena offset the
+    arena-global indices of its elements grouped by partition (ascending inside
+    a partition: the averaged values do not depend on the order, and
+    neighbouring list entries then sit in neighbouring memory).  Partition c of
+    a tensor of `numel` elements in `parts` partitions is the slice [c size +
+    min(c, rem), + size + (c < rem)), size, rem = divmod(numel, parts): for
+    ShuffledSequential that is get_indices' slice of the permutation, for
+    Partitioned the count of {v in 0..numel-1 : v % parts == c}, since argsort
+    is a permutation.  So a step is one {start, count} row per participating
+    tensor and its total is known here, with nothing read back.
+
+    The draws are get_indices' own generator calls in parameter order
+    (torch.randperm(numel) once per tensor; torch.rand(numel).argsort() % parts
+    at first use and whenever the tensor's cycle ends), so the selections and
+    the generator state afterwards are the mask path's.  A skipped tensor (`not
+    requires_grad or grad is None`) has no row, does not advance and is not
+    drawn."""
+
+    ring = 4  # pinned staging slots of the step table
+
+    def __init__(self, selector, layout, n, device):
+        self.selector, self.layout, self.device = selector, layout, torch.device(device)
+        self.shuffled = type(selector) is ShuffledSequentialIndexSelector
+        self.order = torch.zeros(int(n), dtype=torch.int32, device=device)
+        self.cur = [None] * len(layout.numels)  # per tensor: next partition (Partitioned), 0 once drawn (Shuffled)
+        self._slots, self._slot, self._dev = None, 0, None
+
+    def _group(self, i, labels):
+        """order[tensor i] <- its elements' arena indices sorted by partition label (stable)."""
+        off, numel = self.layout.offsets[i], self.layout.numels[i]
+        self.order[off:off + numel].copy_(torch.sort(labels, stable=True).indices + off)
+
+    def step(self, params, skip, iteration):
+        """This step's ([(start, count)] rows with count > 0, total, [redrawn
+        tensor indices]); draws and advances as get_indices would."""
+        L, p = self.layout, self.selector.p
+        rows, redrawn, total = [], [], 0
+        for i, prm in enumerate(params):
+            numel = L.numels[i]
+            if i in skip or numel == 0:
+                continue
+            if self.shuffled:
+                parts = max(1, math.ceil(1.0 / p))
+                size, rem = divmod(numel, parts)
+                if self.cur[i] is None:
+                    perm = torch.randperm(numel, device=prm.device)
+                    pos = torch.arange(numel, device=prm.device)
+                    big = rem * (size + 1)  # positions inside the rem partitions of size + 1
+                    labels = torch.empty_like(pos)
+                    labels[perm] = torch.where(pos < big, pos // (size + 1), rem + (pos - big) // max(size, 1))
+                    self._group(i, labels)
+                    self.cur[i] = 0
+                    redrawn.append(i)
+                c = iteration % parts
+            else:
+                parts = max(1, min(math.ceil(1.0 / p), numel))
+                size, rem = divmod(numel, parts)
+                if self.cur[i] is None or self.cur[i] >= parts:
+                    self._group(i, torch.rand(numel, device=prm.device).argsort() % parts)
+                    self.cur[i] = 0
+                    redrawn.append(i)
+                c = self.cur[i]
+                self.cur[i] += 1
+            count = size + (1 if c < rem else 0)
+            if count:
+                rows.append((L.offsets[i] + c * size + min(c, rem), count))
+                total += count
+        return rows, total, redrawn
+
+    def share(self, redrawn, coll):
+        """With an exchange rank 0's lists win (the reference broadcasts rank 0's
+        masks, sparta.py:32-37): the redrawn tensors' ranges of `order` are
+        broadcast, neighbouring tensors as one run (the alignment gap between
+        them included) -- 4 B per element once per cycle."""
+        L, runs = self.layout, []
+        for i in redrawn:
+            if runs and runs[-1][2] == i - 1:
+                runs[-1][1:] = [L.offsets[i] + L.numels[i], i]
+            else:
+                runs.append([L.offsets[i], L.offsets[i] + L.numels[i], i])
+        for lo, hi, _ in runs:
+            coll.broadcast_(self.order[lo:hi], 0)
+
+    def table(self, rows):
+        """The int32 [T, 3] device table {start, count, prefix} of `rows`, without a
+        host sync: filled into one of `ring` pinned slots (each waits only for its
+        own copy of `ring` steps ago) and copied in stream order."""
+        pre, flat = 0, []
+        for start, count in rows:
+            flat += (start, count, pre)
+            pre += count
+        host = torch.tensor(flat, dtype=torch.int32).view(-1, 3)
+        if self.device.type != "cuda":
+            return host.to(self.device)
+        T = host.shape[0]
+        if self._dev is None or self._dev.shape[0] < T:
+            cap = max(T, len(self.layout.numels))
+            self._dev = torch.empty(cap, 3, dtype=torch.int32, device=self.device)
+            self._slots = [[torch.empty(cap, 3, dtype=torch.int32, pin_memory=True), None] for _ in range(self.ring)]
+        slot = self._slots[self._slot]
+        self._slot = (self._slot + 1) % self.ring
+        if slot[1] is not None:
+            slot[1].synchronize()
+        slot[0][:T].copy_(host)
+        self._dev[:T].copy_(slot[0][:T], non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record()
+        return self._dev[:T]
+
+
 class SparseAverage:
     """SPARTA's per-step orchestration around the Sparta engine, over the
     [K_local, ld] set of one process: one simulated node per process
@@ -356,7 +482,7 @@ class SparseAverage:
 
     def __init__(self):
         self.iteration = 0
-        self.selector = self.engine = None
+        self.selector = self.engine = self.plan = None
         self.draw = MaskDraw()
 
     @property
@@ -365,8 +491,9 @@ class SparseAverage:
 
     @property
     def mask_draw(self):
-        """Which mask draw the last step ran: "philox" | "fused" | "torch"."""
-        return "philox" if self.philox else self.draw.mode
+        """Which mask draw the last step ran: "philox" | "fused" | "torch", or
+        "listed" (no mask: a cycle selector's index lists)."""
+        return "philox" if self.philox else "listed" if self.plan is not None else self.draw.mode
 
     def bind(self, selector, coll, K_local, layout, n, device, dtype):
         """The engine over [K_local, n] sets of arena `layout`; Philox: rank 0's
@@ -379,6 +506,11 @@ class SparseAverage:
             coll.broadcast_(t, 0)
             self.seed = int(t.item())
             self._skip_key = self._skip = None
+        elif (type(selector) in (ShuffledSequentialIndexSelector, PartitionedIndexSelector) and getattr(selector, "listed", False)
+              and torch.device(device).type == "cuda" and hasattr(ops, "sparta_average_listed")):
+            # exactly the two cycle selectors (a subclass may change get_indices) on a GPU arena, opted
+            # in; a stand-in kernel layer (tests) written before the listed kernels keeps the mask path
+            self.plan = ListedPlan(selector, layout, n, device)
         else:
             self.mask = torch.zeros(n, dtype=torch.uint8, device=device)
             self.bits = torch.zeros(ops.sparta_mask_words(n), dtype=torch.int64, device=device)
@@ -423,6 +555,13 @@ class SparseAverage:
         if self.philox:
             self.engine(reps, seed=self.seed, iteration=self.iteration, skip=self._skip_table(self._skipped(params)))
             return
+        if self.plan is not None:  # a cycle selector's lists: no mask, no count read back, its own launch
+            rows, total, redrawn = self.plan.step(params, set(self._skipped(params)), self.iteration)
+            if self.coll.exchange:
+                self.plan.share(redrawn, self.coll)
+            if total:
+                self.engine.listed(reps, self.plan.order, self.plan.table(rows), total)
+            return
         packed = self._draw(params, defer)
         # selected-count bound for Bernoulli masks (no host sync per step); None (exact count read
         # back) for the deterministic-cycle and custom selectors
@@ -432,7 +571,10 @@ class SparseAverage:
     def boundary_bits(self, params):
         """This step's mask as packed words for the one-pass boundary step: the
         draw of __call__ made now instead of inside the SPARTA kernel (the same
-        bits, the generator advanced the same way), or the byte arena packed."""
+        bits, the generator advanced the same way), or the byte arena packed.
+        A listed step keeps no mask: its boundary step runs the two launches."""
+        if self.plan is not None:
+            raise RuntimeError("SPARTA: a listed selector has no mask bits (the boundary step runs two launches)")
         return self.bits if self._draw(params, False) is not None else self.engine.pack(self.mask, self.bits)
 
 

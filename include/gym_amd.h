@@ -561,6 +561,39 @@ GA_API int ga_sparta_average_local(int dtype, void* reps, int64_t K, int64_t ld,
                                    float divisor, int32_t* idx, void* vals,
                                    int64_t cap, int64_t* count, void* work, hipStream_t stream);
 
+/*
+ * SPARTA step of the cycle selectors (ShuffledSequential / Partitioned,
+ * sparta.py:88-193) from index lists instead of a mask.  `order` (int32,
+ * norder entries) holds arena element indices; `table` (int32 [ntens][3],
+ * device) one row {start, count, prefix} per participating tensor: the step
+ * selects order[start .. start + count), prefix = the sum of the counts of the
+ * rows before it, total = the sum of all counts (known on the host: nothing is
+ * read back).  For every packed position j < total, e = order[start_t + j -
+ * prefix_t] of the row t holding j, and each replica's element e becomes
+ * (sum_k reps_k[e]) / divisor, with ga_sparta_average_local's arithmetic (fp32
+ * sum in ascending replica order, correctly rounded quotient for any positive
+ * divisor, rounded once to the set's dtype).  An element must be listed at
+ * most once per step.  Rows with count 0 are allowed; a position whose row,
+ * slot or element index falls outside the table, `order` or [0, n) is
+ * skipped.  total == 0 launches nothing.
+ * Replaces sparta.py:24-44 for those selectors on batched replicas.
+ */
+GA_API int ga_sparta_average_listed(int dtype, void* reps, int64_t K, int64_t ld, int layout, int64_t n,
+                                    const int32_t* order, int64_t norder, const int32_t* table, int32_t ntens,
+                                    int64_t total, float divisor, hipStream_t stream);
+
+/*
+ * The exchange path's gather over the same lists: idx[j] = e and vals[j] =
+ * sum_k src_k[e] for j < total (ga_sparta_select's rounding: the fp32 sum,
+ * rounded once to bf16 on a bf16 set), count[0] = total, count[1] = 0; the
+ * all-reduce of vals and ga_sparta_scatter follow as after ga_sparta_select.
+ * The packed order is list order, not ascending.  total == 0 launches nothing
+ * and leaves count as it is.
+ */
+GA_API int ga_sparta_gather_listed(int dtype, const void* src, int64_t K, int64_t ld, int layout, int64_t n,
+                                   const int32_t* order, int64_t norder, const int32_t* table, int32_t ntens,
+                                   int64_t total, int32_t* idx, void* vals, int64_t* count, hipStream_t stream);
+
 /* ---- DeMo DCT codec ------------------------------------------------------ */
 
 /*
