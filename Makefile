@@ -10,14 +10,14 @@ HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -fvisibility=hidden -Wal
 .PHONY: all clean oracle asan variant
 all: $(LIB)
 
-build/%.o: gym_amd/csrc/%.hip gym_amd/csrc/ga_common.h gym_amd/csrc/adam_math.h gym_amd/csrc/sgd_math.h include/gym_amd.h
+build/%.o: gym_amd/csrc/%.hip gym_amd/csrc/ga_common.h gym_amd/csrc/adam_math.h gym_amd/csrc/sgd_math.h gym_amd/csrc/quant_math.h include/gym_amd.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # topk.hip is built without packed fp32 instructions (its arithmetic is held to one
-# rounded scalar operation per line), and so is sparta_listed.hip; the other files keep the
-# flags they were measured with
-build/topk.o build/topk.s build/sparta_listed.o build/sparta_listed.s: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# rounded scalar operation per line), and so are sparta_listed.hip and mx.hip; the other files
+# keep the flags they were measured with
+build/topk.o build/topk.s build/sparta_listed.o build/sparta_listed.s build/mx.o build/mx.s: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(LIB): $(OBJ)
 	@mkdir -p gym_amd/_lib

@@ -81,6 +81,10 @@ SIGNATURES = {
     "ga_quant_encode": (c_i32, [c_i32, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_p]),
     "ga_diloco_outer_dequant": (c_i32, [c_p, c_i64, c_i64, c_i32, c_i64, c_f32, c_p, c_p, c_i32, c_f32, c_f32,
                                         c_f32, c_f32, c_i32, c_i32, c_p, c_i64, c_i64, c_p]),
+    "ga_mx_row_bytes": (c_i64, [c_i64, c_i32]),
+    "ga_mx_encode": (c_i32, [c_i32, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_p]),
+    "ga_diloco_outer_mx": (c_i32, [c_p, c_i64, c_i64, c_i32, c_i64, c_f32, c_p, c_p, c_i32, c_f32, c_f32,
+                                   c_f32, c_f32, c_i32, c_i32, c_p, c_i64, c_i64, c_p]),
     "ga_topk_row_bytes": (c_i64, [c_i64, c_i32]),
     "ga_topk_encode": (c_i32, [c_i32, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_p]),
     "ga_diloco_outer_sparse": (c_i32, [c_p, c_i64, c_i64, c_i32, c_i64, c_f32, c_p, c_p, c_i32, c_f32, c_f32,

@@ -9,7 +9,7 @@
 // past n in the last block and the pad bytes are written as 0.
 //
 // Arithmetic.  Every line is one individually rounded fp32 operation (rn_add / rn_sub /
-// rn_mul / rn_div below, or an explicit fmaf: nothing here may be contracted,
+// rn_mul / rn_div of quant_math.h, or an explicit fmaf: nothing here may be contracted,
 // tests/quant_checks.py does the same operations one at a time in numpy).
 // Encode, row k, element i, block b (qmax = 127 | 7):
 //   d    = master[i] - float(X[k, i])
@@ -29,6 +29,7 @@
 // diloco_outer_dequant_kernel: the geometry of diloco_outer_kernel (a workgroup owns
 // 1024 vectors, sc1 stores), 4 / 2 payload bytes and one block scale per lane and row.
 #include "ga_common.h"
+#include "quant_math.h"  // rn_add / rn_sub / rn_mul / rn_div, quant_outer_update
 
 namespace ga {
 
@@ -47,27 +48,6 @@ inline int64_t quant_row_bytes(int64_t n, int bits) {
 template <int BITS> struct QMax;
 template <> struct QMax<8> { static constexpr int value = 127; };
 template <> struct QMax<4> { static constexpr int value = 7; };
-
-// One correctly rounded fp32 operation that no neighbour can be fused into.  hipcc
-// contracts a * b + c across statements by default (-ffp-contract=fast-honor-pragmas),
-// and its __fadd_rn / __fmul_rn are the plain operators under that default, so each
-// operation is built here with contraction off.
-__device__ __forceinline__ float rn_add(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ __forceinline__ float rn_sub(float a, float b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
-__device__ __forceinline__ float rn_mul(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float rn_div(float a, float b) {
-#pragma clang fp contract(off)
-    return a / b;
-}
 
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
@@ -169,26 +149,6 @@ __global__ __launch_bounds__(kQThreads) void quant_encode_kernel(
             }
         }
     }
-}
-
-// ga_diloco_outer's element update from the pseudo-gradient on (reduce.hip, outer_update
-// after `g = master - avg`); kept apart from that file so its machine code stays as measured.
-struct QuantOuterParams {
-    float divisor, lr, momentum, dampening, weight_decay;
-    int first_step, nesterov;
-};
-
-__device__ __forceinline__ float quant_outer_update(float acc, float& master, float& buf,
-                                                    const QuantOuterParams& op) {
-    float g = rn_div(acc, op.divisor);
-    if (op.weight_decay != 0.f) g = fmaf(op.weight_decay, master, g);
-    if (op.momentum != 0.f) {
-        if (op.first_step) buf = g;
-        else buf = fmaf(rn_sub(1.f, op.dampening), g, rn_mul(buf, op.momentum));
-        g = op.nesterov ? fmaf(op.momentum, buf, g) : buf;
-    }
-    master = fmaf(-op.lr, g, master);
-    return master;
 }
 
 template <int BITS> __device__ __forceinline__ int sext(uint32_t v) {

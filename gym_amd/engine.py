@@ -11,6 +11,7 @@ node count is K_total = world * K_local.
   DiLoCoOuter  fused outer SGD/Nesterov step        diloco.py:34-76
   DiLoCoOuterAdam  the same with an Adam/AdamW update  diloco.py:26-28
   DiLoCoOuterQuant  the SGD outer step on int8 / int4 block-quantised pseudo-gradients
+  DiLoCoOuterMX     the SGD outer step on mxfp8 / mxfp4 block-float pseudo-gradients
   DiLoCoOuterTopK  the SGD outer step on top-k sparse pseudo-gradients (k per 4096-element chunk, error feedback)
   DiLoCoOuterStream  the SGD outer step sent at one step, merged `delay` steps later and mixed into the rows
   DiLoCoOuterIslands  the SGD outer step per node against its island's average, per-node master and momentum
@@ -551,10 +552,14 @@ class DiLoCoOuterQuant:
     quantisation dropped from a node's delta is added to its next one.  No
     placement search and no masked (SPARTA boundary) step."""
 
+    # the gym_amd.ops entries of the format (row bytes, encode, decode + outer step) and its name
+    _ops = ("quant_row_bytes", "quant_encode", "diloco_outer_dequant")
+    _what = "quantised"
+
     def __init__(self, coll: Collective, K_local, n, device, dtype, bits=8, error_feedback=False, lr=0.7,
                  momentum=0.9, nesterov=True, dampening=0.0, weight_decay=0.0, placement=True):
         if bits not in (4, 8):
-            raise ValueError(f"DiLoCoOuterQuant: bits={bits!r} is not 4 or 8")
+            raise ValueError(f"{type(self).__name__}: bits={bits!r} is not 4 or 8")
         self.coll, self.K_local, self.n, self.bits = coll, int(K_local), int(n), int(bits)
         self.K_total = coll.world * self.K_local
         self.hp = dict(lr=lr, momentum=momentum, nesterov=nesterov, dampening=dampening, weight_decay=weight_decay)
@@ -564,12 +569,12 @@ class DiLoCoOuterQuant:
         self.mom = self._state[self.n:] if momentum != 0 else None
         self.residual = (torch.zeros(self.K_local, self.n, device=device, dtype=torch.float32)
                          if error_feedback else None)
-        self.payload_bytes_per_node = ops.quant_row_bytes(self.n, self.bits)
+        self.payload_bytes_per_node = getattr(ops, self._ops[0])(self.n, self.bits)
         self.payload = torch.zeros(self.K_total, self.payload_bytes_per_node, device=device, dtype=torch.uint8)
-        self.placement = {"placed": False, "why": "no search for the quantised outer step"}
+        self.placement = {"placed": False, "why": f"no search for the {self._what} outer step"}
         self.relocate_replicas = None  # accepted as on DiLoCoOuter; the set stays where it is
         self.first = True
-        self.launch_elems = []  # elements per ga_diloco_outer_dequant launch of the last step
+        self.launch_elems = []  # elements per decode launch of the last step
 
     def init_master(self, params_flat):
         """master <- the node's initial parameters (diloco.py:81-82); no error carried over."""
@@ -580,18 +585,42 @@ class DiLoCoOuterQuant:
 
     def __call__(self, reps, sparse_mask=None):
         if sparse_mask is not None:
-            raise ValueError("DiLoCoOuterQuant: no one-pass masked outer step; run Sparta and the outer step one "
-                             "after the other")
+            raise ValueError(f"{type(self).__name__}: no one-pass masked outer step; run Sparta and the outer step "
+                             "one after the other")
         n, K, h = self.n, self.K_local, self.hp
         a = self.coll.rank * K
         own = self.payload[a:a + K]
-        ops.quant_encode(reps[:, :n], self.master, self.residual, own, n, self.bits)
+        getattr(ops, self._ops[1])(reps[:, :n], self.master, self.residual, own, n, self.bits)
         if self.coll.exchange:
             self.coll.all_gather_into(self.payload.view(-1), own.view(-1))
-        ops.diloco_outer_dequant(self.payload, self.master, self.mom, reps[:, :n], n, self.bits, self.K_total,
-                                 h["lr"], h["momentum"], h["dampening"], h["weight_decay"], h["nesterov"], self.first)
+        getattr(ops, self._ops[2])(self.payload, self.master, self.mom, reps[:, :n], n, self.bits, self.K_total,
+                                   h["lr"], h["momentum"], h["dampening"], h["weight_decay"], h["nesterov"],
+                                   self.first)
         self.launch_elems = [n]
         self.first = False
+
+
+MX_FORMATS = {"mxfp8": 8, "mxfp4": 4}  # outer_compression strings: OCP MX E4M3 / E2M1 elements
+
+
+class DiLoCoOuterMX(DiLoCoOuterQuant):
+    """DiLoCo's outer step (SGD family) on MX block-float pseudo-gradients, with
+    DiLoCoOuterQuant's call surface and state.
+
+    Every node sends its pseudo-gradient master - x_k as OCP MX blocks: 32 elements
+    of E4M3 (bits=8) or E2M1 (bits=4), each block with one power-of-two E8M0 scale
+    byte (ga_mx_encode: 8.25 / 4.25 bits per element).  The payload rows are
+    all-gathered in node order, and one launch per process decodes all K_total rows in
+    ascending node order, averages them and takes the outer update
+    (ga_diloco_outer_mx), so all nodes end bit-identical without a broadcast.
+
+    Master and momentum are fp32 and REPLICATED on every process, not sharded (8 B
+    per parameter per rank).  error_feedback keeps a [K_local, n] fp32 residual: what
+    rounding dropped from a node's delta is added to its next one.  No placement
+    search and no masked (SPARTA boundary) step."""
+
+    _ops = ("mx_row_bytes", "mx_encode", "diloco_outer_mx")
+    _what = "MX"
 
 
 TOPK_MAX = 256  # entries per 4096-element chunk, ga_topk_encode's limit

@@ -25,6 +25,11 @@ all-gather of the payload rows, ga_diloco_outer_dequant), outer_error_feedback=T
 carries each node's quantisation error into its next outer step.  SGD-family outer
 optimizers only; the master and momentum are then replicated on every rank.
 
+outer_compression="mxfp8" | "mxfp4" exchanges them as OCP MX block floats instead: 32
+elements of E4M3 / E2M1 under one power-of-two scale byte (engine.DiLoCoOuterMX:
+ga_mx_encode, one all-gather, ga_diloco_outer_mx; 8.25 / 4.25 bits per element), with
+the same options and restrictions as the integer formats.
+
 outer_compression="topk" sends the outer_topk (default 32, 1..256) largest-magnitude
 entries of every 4096-element chunk of the pseudo-gradient as (fp32 value, uint16
 index) pairs (engine.DiLoCoOuterTopK: ga_topk_encode, one all-gather,
@@ -48,8 +53,8 @@ from typing import Optional, Union
 import torch
 
 from .. import ops
-from ..engine import (QUANT_BITS, DiLoCoOuter, DiLoCoOuterAdam, DiLoCoOuterQuant, DiLoCoOuterStream, DiLoCoOuterTopK,
-                      FragmentedOuter, TorchOuter, check_topk, fragment_bounds)
+from ..engine import (MX_FORMATS, QUANT_BITS, DiLoCoOuter, DiLoCoOuterAdam, DiLoCoOuterMX, DiLoCoOuterQuant,
+                      DiLoCoOuterStream, DiLoCoOuterTopK, FragmentedOuter, TorchOuter, check_topk, fragment_bounds)
 from .communicate_optimize_strategy import CommunicationModule
 from .optim import OptimSpec, ensure_optim_spec
 from .strategy import Strategy, build_inner_optimizer, clip_and_step
@@ -108,9 +113,10 @@ def check_outer_compression(compression, spec, topk=32):
     not looked at for any other compression."""
     if compression is None:
         return None
-    if not isinstance(compression, str) or (compression != TOPK and compression not in QUANT_BITS):
+    formats = {**QUANT_BITS, **MX_FORMATS}
+    if not isinstance(compression, str) or (compression != TOPK and compression not in formats):
         raise ValueError(f"outer_compression={compression!r}: expected None, "
-                         + " or ".join(map(repr, [*QUANT_BITS, TOPK])))
+                         + " or ".join(map(repr, [*formats, TOPK])))
     if fused_sgd_hparams(spec) is None:
         raise ValueError(f"outer_compression={compression!r} needs a plain torch.optim.SGD outer optimizer (the "
                          f"quantised and sparse outer steps have no other update); got {spec.cls.__name__} with "
@@ -118,7 +124,7 @@ def check_outer_compression(compression, spec, topk=32):
     if compression == TOPK:
         check_topk(topk)
         return TOPK
-    return QUANT_BITS[compression]
+    return formats[compression]
 
 
 def _is_int(x):
@@ -164,8 +170,8 @@ def build_outer_engine(strategy, spec, coll, K_local, n, device, dtype, placemen
     strategy was built with fused_outer=False (the A/B switch against torch's
     optimizer; SGD specs are always fused), TorchOuter (torch's optimizer on an
     fp32 master) for every other spec.  With outer_compression set:
-    DiLoCoOuterQuant ("int8" / "int4") or DiLoCoOuterTopK ("topk", k = outer_topk)
-    for plain SGD, ValueError for anything else.  placement: the engine's placement
+    DiLoCoOuterQuant ("int8" / "int4"), DiLoCoOuterMX ("mxfp8" / "mxfp4") or DiLoCoOuterTopK
+    ("topk", k = outer_topk) for plain SGD, ValueError for anything else.  placement: the engine's placement
     option, None for the strategy's."""
     placement = strategy.placement_opt if placement is None else placement
     bits = check_outer_compression(strategy.kwargs.get("outer_compression"), spec,
@@ -176,6 +182,9 @@ def build_outer_engine(strategy, spec, coll, K_local, n, device, dtype, placemen
                                placement=placement,
                                error_feedback=bool(strategy.kwargs.get("outer_error_feedback", False)), **hp)
     if bits is not None:
+        if strategy.kwargs.get("outer_compression") in MX_FORMATS:
+            return DiLoCoOuterMX(coll, K_local, n, device, dtype, bits=bits, placement=placement,
+                                 error_feedback=bool(strategy.kwargs.get("outer_error_feedback", False)), **hp)
         return DiLoCoOuterQuant(coll, K_local, n, device, dtype, bits=bits, placement=placement,
                                 error_feedback=bool(strategy.kwargs.get("outer_error_feedback", False)), **hp)
     if hp is not None:
@@ -191,7 +200,7 @@ def build_streaming_outer(strategy, spec, coll, K_local, n, device, dtype, offse
     [K_local, n] set whose tensors start at `offsets`: the arena cut by
     engine.fragment_bounds in units of 512 * world elements, one engine per fragment
     -- DiLoCoOuterStream with a delay or a mix, otherwise whatever build_outer_engine
-    chooses for the spec (DiLoCoOuter, DiLoCoOuterAdam, DiLoCoOuterQuant, DiLoCoOuterTopK), without a
+    chooses for the spec (DiLoCoOuter, DiLoCoOuterAdam, DiLoCoOuterQuant, DiLoCoOuterMX, DiLoCoOuterTopK), without a
     placement search and with n the fragment's length.  A spec that takes torch's
     optimizer (TorchOuter) has no fragments."""
     F, delay, mix = opts

@@ -388,6 +388,59 @@ GA_API int ga_diloco_outer_dequant(const void* payload, int64_t S, int64_t ld_q_
                                    float momentum, float dampening, float weight_decay, int nesterov, int dtype,
                                    void* dst, int64_t K_out, int64_t ld_dst, hipStream_t stream);
 
+/* ---- DiLoCo outer step on MX fp8 / fp4 block-float pseudo-gradients ------ */
+
+/*
+ * The MX format, on the wire and in memory (OCP Microscaling, scale rounded up so no
+ * element saturates; no reference counterpart).  Blocks are 32 consecutive elements
+ * of an arena row, nb = ceil(n / 32), the last may be short; bits is 8 (E4M3, as
+ * torch's float8_e4m3fn; 0x7F / 0xFF never produced) or 4 (E2M1: magnitudes 0, 0.5,
+ * 1, 1.5, 2, 3, 4, 6, bit 3 of the nibble the sign).  One payload row per node:
+ *   [ elements : nb * 32 * bits / 8 ][ scales : nb x 1 byte ]
+ * bits = 4: byte j holds element 2j in bits 0-3 and element 2j + 1 in bits 4-7.  A
+ * scale byte b is E8M0: 2^(b - 127).  Elements past n and the pad bytes are 0.
+ * ga_mx_row_bytes: that size rounded up to a multiple of 16 (host only; -1 for
+ * n < 0 or bits outside {4, 8}).
+ */
+GA_API int64_t ga_mx_row_bytes(int64_t n, int bits);
+
+/*
+ * Encode the pseudo-gradients of K rows x [K, ld_x] (f32 / bf16) against an fp32
+ * master into K payload rows (row k at payload + k * ld_q_bytes).  Every line is one
+ * individually rounded fp32 operation:
+ *   d    = master[i] - float(x[k, i])
+ *   d    = d + residual[k, i]                  (residual != null: error feedback)
+ *   amax = max over the block of |d|           (a NaN in the block makes amax NaN)
+ *   !(amax >= 2^-100) or amax infinite:  b = 0 and every element of the block = +0
+ *   else  E, M = biased exponent and 23-bit mantissa field of amax
+ *         b = E - 8 + (M > 0x600000)  (bits = 8)  |  E - 2 + (M > 0x400000)  (bits = 4)
+ *         element = d * 2^-(b - 127) rounded to nearest even on the element grid, the
+ *         sign kept (a negative value that rounds to zero is 0x80 | nibble 0x8)
+ *   residual[k, i] = d - element * 2^(b - 127) (residual != null; the product is exact)
+ * amax * 2^-(b - 127) never exceeds 448 | 6 and b is in 19..253.  residual is an
+ * fp32 [K, ld_r] set or null.  ld_q_bytes >= ga_mx_row_bytes(n, bits) and a multiple
+ * of 16, payload 16-byte aligned; bytes of a payload row past its row_bytes are not
+ * written.  x / master / residual may have any element alignment and ld (16-byte
+ * vector access when aligned, element access otherwise, the same bytes either way).
+ */
+GA_API int ga_mx_encode(int dtype, const void* x, int64_t K, int64_t ld_x, const float* master,
+                        float* residual, int64_t ld_r, int64_t n, int bits, void* payload,
+                        int64_t ld_q_bytes, hipStream_t stream);
+
+/*
+ * Decode S payload rows (ga_mx_encode's format, row r at payload + r * ld_q_bytes,
+ * node order) and take the outer step, one pass over n elements:
+ *   acc = 0; for r in 0..S-1: acc = acc + element_r[i] * 2^(b_r[block of i] - 127)
+ *   g   = acc / divisor
+ *   then exactly ga_diloco_outer_dequant's update and write-back of K_out rows.
+ * The arguments and their checks are ga_diloco_outer_dequant's.  Algorithmic bytes
+ * per element: S * (bits / 8 + 1 / 32) + 16 (8 without momentum) + K_out * sizeof(dtype).
+ */
+GA_API int ga_diloco_outer_mx(const void* payload, int64_t S, int64_t ld_q_bytes, int bits, int64_t n,
+                              float divisor, float* master, float* mom, int first_step, float lr,
+                              float momentum, float dampening, float weight_decay, int nesterov, int dtype,
+                              void* dst, int64_t K_out, int64_t ld_dst, hipStream_t stream);
+
 /* ---- DiLoCo outer step on top-k sparse pseudo-gradients ----------------- */
 
 /*
