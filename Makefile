@@ -15,9 +15,9 @@ build/%.o: gym_amd/csrc/%.hip gym_amd/csrc/ga_common.h gym_amd/csrc/adam_math.h 
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # topk.hip is built without packed fp32 instructions (its arithmetic is held to one
-# rounded scalar operation per line), and so are sparta_listed.hip and mx.hip; the other files
+# rounded scalar operation per line), and so are sparta_listed.hip, mx.hip and rht.hip; the other files
 # keep the flags they were measured with
-build/topk.o build/topk.s build/sparta_listed.o build/sparta_listed.s build/mx.o build/mx.s: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+build/topk.o build/topk.s build/sparta_listed.o build/sparta_listed.s build/mx.o build/mx.s build/rht.o build/rht.s: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(LIB): $(OBJ)
 	@mkdir -p gym_amd/_lib

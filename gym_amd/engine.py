@@ -12,6 +12,7 @@ node count is K_total = world * K_local.
   DiLoCoOuterAdam  the same with an Adam/AdamW update  diloco.py:26-28
   DiLoCoOuterQuant  the SGD outer step on int8 / int4 block-quantised pseudo-gradients
   DiLoCoOuterMX     the SGD outer step on mxfp8 / mxfp4 block-float pseudo-gradients
+  DiLoCoOuterRHT    the SGD outer step on Hadamard-rotated int8 / int4 pseudo-gradients
   DiLoCoOuterTopK  the SGD outer step on top-k sparse pseudo-gradients (k per 4096-element chunk, error feedback)
   DiLoCoOuterStream  the SGD outer step sent at one step, merged `delay` steps later and mixed into the rows
   DiLoCoOuterIslands  the SGD outer step per node against its island's average, per-node master and momentum
@@ -555,6 +556,7 @@ class DiLoCoOuterQuant:
     # the gym_amd.ops entries of the format (row bytes, encode, decode + outer step) and its name
     _ops = ("quant_row_bytes", "quant_encode", "diloco_outer_dequant")
     _what = "quantised"
+    _op_args = ()  # what the format's encode and decode take behind the shared arguments
 
     def __init__(self, coll: Collective, K_local, n, device, dtype, bits=8, error_feedback=False, lr=0.7,
                  momentum=0.9, nesterov=True, dampening=0.0, weight_decay=0.0, placement=True):
@@ -590,12 +592,12 @@ class DiLoCoOuterQuant:
         n, K, h = self.n, self.K_local, self.hp
         a = self.coll.rank * K
         own = self.payload[a:a + K]
-        getattr(ops, self._ops[1])(reps[:, :n], self.master, self.residual, own, n, self.bits)
+        getattr(ops, self._ops[1])(reps[:, :n], self.master, self.residual, own, n, self.bits, *self._op_args)
         if self.coll.exchange:
             self.coll.all_gather_into(self.payload.view(-1), own.view(-1))
         getattr(ops, self._ops[2])(self.payload, self.master, self.mom, reps[:, :n], n, self.bits, self.K_total,
                                    h["lr"], h["momentum"], h["dampening"], h["weight_decay"], h["nesterov"],
-                                   self.first)
+                                   self.first, *self._op_args)
         self.launch_elems = [n]
         self.first = False
 
@@ -621,6 +623,42 @@ class DiLoCoOuterMX(DiLoCoOuterQuant):
 
     _ops = ("mx_row_bytes", "mx_encode", "diloco_outer_mx")
     _what = "MX"
+
+
+RHT_FORMATS = {"rht-int8": 8, "rht-int4": 4}  # outer_compression strings: rotated int8 / int4 blocks
+
+
+def check_rotation_seed(seed):
+    """outer_rotation_seed as an int; ValueError unless it is an integer in 0..2^32 - 1."""
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 32:
+        raise ValueError(f"outer_rotation_seed={seed!r}: expected an integer with 0 <= outer_rotation_seed < 2^32")
+    return int(seed)
+
+
+class DiLoCoOuterRHT(DiLoCoOuterQuant):
+    """DiLoCo's outer step (SGD family) on Hadamard-rotated int8 / int4 pseudo-gradients,
+    with DiLoCoOuterQuant's call surface, state and payload row.
+
+    Every node multiplies each 256-element block of its pseudo-gradient master - x_k by
+    a sign diagonal drawn from `seed` (the same on every rank), Walsh-Hadamard transforms
+    it and quantises the rotated block as DiLoCoOuterQuant does (ga_rht_encode): an
+    outlier is spread over the block instead of setting its scale alone.  The payload
+    rows are all-gathered in node order, and one launch per process adds all K_total rows
+    in the rotated domain in ascending node order, rotates the sum back once per block
+    and takes the outer update (ga_diloco_outer_rht), so all nodes end bit-identical
+    without a broadcast.  The bytes sent are DiLoCoOuterQuant's.
+
+    error_feedback keeps a [K_local, n] fp32 residual in the unrotated domain: what
+    quantisation dropped from a node's delta is added to its next one.  A fragment's
+    engine counts the sign diagonal from its own start."""
+
+    _ops = ("quant_row_bytes", "rht_encode", "diloco_outer_rht")
+    _what = "rotated quantised"
+
+    def __init__(self, *args, seed=0, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.seed = check_rotation_seed(seed)
+        self._op_args = (self.seed,)
 
 
 TOPK_MAX = 256  # entries per 4096-element chunk, ga_topk_encode's limit

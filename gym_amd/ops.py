@@ -365,8 +365,9 @@ def _payload_ld(who, payload, rows, n, bits, row_bytes=None):
     return ld
 
 
-def _block_encode(who, entry, row_bytes, x, master, residual, payload, n, bits):
-    """ga_quant_encode / ga_mx_encode (one argument list) on a replica set."""
+def _block_encode(who, entry, row_bytes, x, master, residual, payload, n, bits, extra=()):
+    """ga_quant_encode / ga_mx_encode / ga_rht_encode (one argument list, `extra` before the
+    stream) on a replica set."""
     x2 = _as2d(x)
     r2 = _as2d(residual) if residual is not None else None
     _gpu(x2, master, r2, payload)
@@ -383,12 +384,13 @@ def _block_encode(who, entry, row_bytes, x, master, residual, payload, n, bits):
         ldr = _rows_ld(r2)[1]
     ldq = _payload_ld(who, payload, K, n, bits, row_bytes)
     check(getattr(lib(), entry)(_dtype_code(x2), _p(x2), K, ldx, _p(master), _p(r2), ldr, n, int(bits), _p(payload),
-                                ldq, _stream()), entry)
+                                ldq, *extra, _stream()), entry)
 
 
 def _block_outer(who, entry, row_bytes, payload, master, mom, dst, n, bits, divisor, lr, momentum, dampening,
-                 weight_decay, nesterov, first_step):
-    """ga_diloco_outer_dequant / ga_diloco_outer_mx (one argument list)."""
+                 weight_decay, nesterov, first_step, extra=()):
+    """ga_diloco_outer_dequant / ga_diloco_outer_mx / ga_diloco_outer_rht (one argument list,
+    `extra` before the stream)."""
     dst2 = _as2d(dst) if dst is not None else None
     _gpu(payload, master, mom, dst2)
     n = int(n)
@@ -405,7 +407,8 @@ def _block_outer(who, entry, row_bytes, payload, master, mom, dst, n, bits, divi
     code = _dtype_code(dst2) if dst2 is not None else _lib.GA_F32
     check(getattr(lib(), entry)(_p(payload), S, ldq, int(bits), n, float(divisor), _p(master), _p(mom),
                                 int(bool(first_step)), float(lr), float(momentum), float(dampening),
-                                float(weight_decay), int(bool(nesterov)), code, _p(dst2), Ko, ldd, _stream()), entry)
+                                float(weight_decay), int(bool(nesterov)), code, _p(dst2), Ko, ldd, *extra, _stream()),
+          entry)
 
 
 def quant_encode(x, master, residual, payload, n, bits):
@@ -447,6 +450,31 @@ def diloco_outer_mx(payload, master, mom, dst, n, bits, divisor, lr, momentum, d
     dst <- the new master."""
     _block_outer("diloco_outer_mx", "ga_diloco_outer_mx", mx_row_bytes, payload, master, mom, dst, n, bits, divisor,
                  lr, momentum, dampening, weight_decay, nesterov, first_step)
+
+
+def _rotation_seed(who, seed):
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 32:
+        raise ValueError(f"{who}: seed={seed!r} must be an integer in 0..2^32 - 1")
+    return seed
+
+
+def rht_encode(x, master, residual, payload, n, bits, seed):
+    """payload[k] <- the int8 / int4 pseudo-gradient master - x[k] (+ residual[k], which then
+    takes the quantisation error) of every row k of the replica set x, each 256-element
+    block quantised after the sign diagonal of `seed` and a Walsh-Hadamard transform
+    (ga_rht_encode; payload: uint8 [K, >= quant_row_bytes(n, bits)], quant_encode's row)."""
+    _block_encode("rht_encode", "ga_rht_encode", quant_row_bytes, x, master, residual, payload, n, bits,
+                  extra=(_rotation_seed("rht_encode", seed),))
+
+
+def diloco_outer_rht(payload, master, mom, dst, n, bits, divisor, lr, momentum, dampening, weight_decay, nesterov,
+                     first_step, seed):
+    """The DiLoCo outer step on the S rotated payload rows: summed in the rotated domain,
+    rotated back once per block, over divisor (ga_diloco_outer_rht): master / mom (fp32)
+    updated as by diloco_outer, every row of dst <- the new master."""
+    _block_outer("diloco_outer_rht", "ga_diloco_outer_rht", quant_row_bytes, payload, master, mom, dst, n, bits,
+                 divisor, lr, momentum, dampening, weight_decay, nesterov, first_step,
+                 extra=(_rotation_seed("diloco_outer_rht", seed),))
 
 
 def topk_row_bytes(n, k):

@@ -30,6 +30,15 @@ elements of E4M3 / E2M1 under one power-of-two scale byte (engine.DiLoCoOuterMX:
 ga_mx_encode, one all-gather, ga_diloco_outer_mx; 8.25 / 4.25 bits per element), with
 the same options and restrictions as the integer formats.
 
+outer_compression="rht-int8" | "rht-int4" sends the integer formats' payload, byte for
+byte in size and layout, quantised in a rotated basis: every 256-element block is
+multiplied by a sign diagonal and Walsh-Hadamard transformed before its scale is taken,
+so an outlier is spread over the block instead of flattening it (engine.DiLoCoOuterRHT:
+ga_rht_encode, one all-gather, ga_diloco_outer_rht, which adds the rows in the rotated
+domain and rotates back once).  outer_rotation_seed (default 0, the same on every rank)
+selects the sign diagonal and is ignored for any other compression.  Same options and
+restrictions as the integer formats.
+
 outer_compression="topk" sends the outer_topk (default 32, 1..256) largest-magnitude
 entries of every 4096-element chunk of the pseudo-gradient as (fp32 value, uint16
 index) pairs (engine.DiLoCoOuterTopK: ga_topk_encode, one all-gather,
@@ -53,8 +62,9 @@ from typing import Optional, Union
 import torch
 
 from .. import ops
-from ..engine import (MX_FORMATS, QUANT_BITS, DiLoCoOuter, DiLoCoOuterAdam, DiLoCoOuterMX, DiLoCoOuterQuant,
-                      DiLoCoOuterStream, DiLoCoOuterTopK, FragmentedOuter, TorchOuter, check_topk, fragment_bounds)
+from ..engine import (MX_FORMATS, QUANT_BITS, RHT_FORMATS, DiLoCoOuter, DiLoCoOuterAdam, DiLoCoOuterMX,
+                      DiLoCoOuterQuant, DiLoCoOuterRHT, DiLoCoOuterStream, DiLoCoOuterTopK, FragmentedOuter, TorchOuter,
+                      check_rotation_seed, check_topk, fragment_bounds)
 from .communicate_optimize_strategy import CommunicationModule
 from .optim import OptimSpec, ensure_optim_spec
 from .strategy import Strategy, build_inner_optimizer, clip_and_step
@@ -106,14 +116,15 @@ def fused_adam_hparams(spec: OptimSpec):
                 weight_decay=float(weight_decay), decoupled=decoupled)
 
 
-def check_outer_compression(compression, spec, topk=32):
+def check_outer_compression(compression, spec, topk=32, rotation_seed=0):
     """The bit width of outer_compression (None: off; TOPK itself for "topk", after
     outer_topk = `topk` was checked) for outer OptimSpec `spec`; ValueError for an
     unknown string or an outer optimizer without a compressed step.  outer_topk is
-    not looked at for any other compression."""
+    not looked at for any other compression, outer_rotation_seed = `rotation_seed` only
+    for the rotated formats."""
     if compression is None:
         return None
-    formats = {**QUANT_BITS, **MX_FORMATS}
+    formats = {**QUANT_BITS, **MX_FORMATS, **RHT_FORMATS}
     if not isinstance(compression, str) or (compression != TOPK and compression not in formats):
         raise ValueError(f"outer_compression={compression!r}: expected None, "
                          + " or ".join(map(repr, [*formats, TOPK])))
@@ -124,6 +135,8 @@ def check_outer_compression(compression, spec, topk=32):
     if compression == TOPK:
         check_topk(topk)
         return TOPK
+    if compression in RHT_FORMATS:
+        check_rotation_seed(rotation_seed)
     return formats[compression]
 
 
@@ -170,12 +183,13 @@ def build_outer_engine(strategy, spec, coll, K_local, n, device, dtype, placemen
     strategy was built with fused_outer=False (the A/B switch against torch's
     optimizer; SGD specs are always fused), TorchOuter (torch's optimizer on an
     fp32 master) for every other spec.  With outer_compression set:
-    DiLoCoOuterQuant ("int8" / "int4"), DiLoCoOuterMX ("mxfp8" / "mxfp4") or DiLoCoOuterTopK
-    ("topk", k = outer_topk) for plain SGD, ValueError for anything else.  placement: the engine's placement
+    DiLoCoOuterQuant ("int8" / "int4"), DiLoCoOuterMX ("mxfp8" / "mxfp4"), DiLoCoOuterRHT ("rht-int8" /
+    "rht-int4", seed = outer_rotation_seed) or DiLoCoOuterTopK ("topk", k = outer_topk) for plain SGD, ValueError for anything else.  placement: the engine's placement
     option, None for the strategy's."""
     placement = strategy.placement_opt if placement is None else placement
     bits = check_outer_compression(strategy.kwargs.get("outer_compression"), spec,
-                                   strategy.kwargs.get("outer_topk", 32))
+                                   strategy.kwargs.get("outer_topk", 32),
+                                   strategy.kwargs.get("outer_rotation_seed", 0))
     hp = fused_sgd_hparams(spec)
     if bits == TOPK:
         return DiLoCoOuterTopK(coll, K_local, n, device, dtype, k=strategy.kwargs.get("outer_topk", 32),
@@ -185,6 +199,10 @@ def build_outer_engine(strategy, spec, coll, K_local, n, device, dtype, placemen
         if strategy.kwargs.get("outer_compression") in MX_FORMATS:
             return DiLoCoOuterMX(coll, K_local, n, device, dtype, bits=bits, placement=placement,
                                  error_feedback=bool(strategy.kwargs.get("outer_error_feedback", False)), **hp)
+        if strategy.kwargs.get("outer_compression") in RHT_FORMATS:
+            return DiLoCoOuterRHT(coll, K_local, n, device, dtype, bits=bits, placement=placement,
+                                  seed=strategy.kwargs.get("outer_rotation_seed", 0),
+                                  error_feedback=bool(strategy.kwargs.get("outer_error_feedback", False)), **hp)
         return DiLoCoOuterQuant(coll, K_local, n, device, dtype, bits=bits, placement=placement,
                                 error_feedback=bool(strategy.kwargs.get("outer_error_feedback", False)), **hp)
     if hp is not None:
@@ -200,7 +218,8 @@ def build_streaming_outer(strategy, spec, coll, K_local, n, device, dtype, offse
     [K_local, n] set whose tensors start at `offsets`: the arena cut by
     engine.fragment_bounds in units of 512 * world elements, one engine per fragment
     -- DiLoCoOuterStream with a delay or a mix, otherwise whatever build_outer_engine
-    chooses for the spec (DiLoCoOuter, DiLoCoOuterAdam, DiLoCoOuterQuant, DiLoCoOuterMX, DiLoCoOuterTopK), without a
+    chooses for the spec (DiLoCoOuter, DiLoCoOuterAdam, DiLoCoOuterQuant, DiLoCoOuterMX, DiLoCoOuterRHT,
+    DiLoCoOuterTopK), without a
     placement search and with n the fragment's length.  A spec that takes torch's
     optimizer (TorchOuter) has no fragments."""
     F, delay, mix = opts
@@ -274,17 +293,18 @@ class DiLoCoStrategy(Strategy):
                  outer_optim_spec: Optional[Union[str, OptimSpec]] = None, H: int = 100,
                  outer_compression: Optional[str] = None, outer_error_feedback: bool = False,
                  num_fragments: int = 1, outer_delay: int = 0, outer_mix: float = 0.0, outer_topk: int = 32,
-                 **kwargs):
+                 outer_rotation_seed: int = 0, **kwargs):
         self.inner_optim_spec = ensure_optim_spec(optim_spec, OptimSpec(torch.optim.AdamW))
         self.outer_optim_spec = ensure_optim_spec(outer_optim_spec, default_outer_spec())
         self.H = H
-        check_outer_compression(outer_compression, self.outer_optim_spec, outer_topk)
+        check_rotation_seed(outer_rotation_seed)
+        check_outer_compression(outer_compression, self.outer_optim_spec, outer_topk, outer_rotation_seed)
         num_fragments, outer_delay, outer_mix = check_streaming(num_fragments, outer_delay, outer_mix, H,
                                                                 self.outer_optim_spec, outer_compression)
         # all reach build_outer_engine / build_streaming_outer through self.kwargs, as fused_outer does
         super().__init__(outer_compression=outer_compression, outer_error_feedback=bool(outer_error_feedback),
                          num_fragments=num_fragments, outer_delay=outer_delay, outer_mix=outer_mix,
-                         outer_topk=outer_topk, **kwargs)
+                         outer_topk=outer_topk, outer_rotation_seed=outer_rotation_seed, **kwargs)
 
     def _init_node(self, model, rank, num_nodes):
         super()._init_node(model, rank, num_nodes)

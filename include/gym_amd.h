@@ -441,6 +441,48 @@ GA_API int ga_diloco_outer_mx(const void* payload, int64_t S, int64_t ld_q_bytes
                               float momentum, float dampening, float weight_decay, int nesterov, int dtype,
                               void* dst, int64_t K_out, int64_t ld_dst, hipStream_t stream);
 
+/* ---- DiLoCo outer step on Hadamard-rotated int8 / int4 pseudo-gradients -- */
+
+/*
+ * ga_quant_encode's payload row, byte for byte in layout (ga_quant_row_bytes gives its
+ * size), quantised in a randomly rotated basis: each 256-element block (a short last
+ * block zero-padded to 256) is multiplied by a sign diagonal and Walsh-Hadamard
+ * transformed before the block scale is taken.  Every line below is one individually
+ * rounded fp32 operation.
+ *   sigma_i = -1 when bit (i & 31) of fmix32((uint32)(i >> 5) + seed * 0x9E3779B9) is
+ *             set, else +1; fmix32 is murmur3's 32-bit finaliser, i the index in the row
+ *             the call was handed; the product with sigma flips the sign bit
+ *   FWHT256(v): for h = 1, 2, 4, .., 128, for every j with bit h clear:
+ *               (v_j, v_{j+h}) <- (v_j + v_{j+h}, v_j - v_{j+h});  then v_j <- v_j * 2^-4
+ * Encode, row k, block B:
+ *   d    = master[i] - float(x[k, i])
+ *   d    = d + residual[k, i]                  (residual != null: error feedback)
+ *   y    = FWHT256(sigma * d)
+ *   amax = max over the block of |y|           (a NaN in the block makes amax NaN)
+ *   !(amax >= 2^-100) or amax infinite:  s = 0 and every q of the block = 0
+ *   else  s = amax / qmax, inv = qmax / amax, q = clamp((int)rintf(y * inv), -qmax, qmax)
+ *   scales[k, B] = s
+ *   w = FWHT256(float(q) * s);  residual[k, i] = d - sigma_i * w_i    (residual != null, i < n)
+ * The arguments and their checks are ga_quant_encode's; seed is the same on every node.
+ */
+GA_API int ga_rht_encode(int dtype, const void* x, int64_t K, int64_t ld_x, const float* master,
+                         float* residual, int64_t ld_r, int64_t n, int bits, void* payload,
+                         int64_t ld_q_bytes, uint32_t seed, hipStream_t stream);
+
+/*
+ * Decode S payload rows (ga_rht_encode's, node order) and take the outer step.  The rows
+ * are summed in the rotated domain and rotated back once per block, whatever S is:
+ *   acc = 0; for r in 0..S-1: acc = acc + float(q_r[i]) * s_r[block of i]
+ *   w   = FWHT256(acc);   g = (sigma_i * w_i) / divisor
+ *   then exactly ga_diloco_outer_dequant's update and write-back of K_out rows.
+ * The arguments and their checks are ga_diloco_outer_dequant's; seed is the encode's.
+ * S has no upper limit.  Algorithmic bytes per element as for ga_diloco_outer_dequant.
+ */
+GA_API int ga_diloco_outer_rht(const void* payload, int64_t S, int64_t ld_q_bytes, int bits, int64_t n,
+                               float divisor, float* master, float* mom, int first_step, float lr,
+                               float momentum, float dampening, float weight_decay, int nesterov, int dtype,
+                               void* dst, int64_t K_out, int64_t ld_dst, uint32_t seed, hipStream_t stream);
+
 /* ---- DiLoCo outer step on top-k sparse pseudo-gradients ----------------- */
 
 /*
