@@ -88,6 +88,13 @@ SIGNATURES = {
     "ga_rht_encode": (c_i32, [c_i32, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_u32, c_p]),
     "ga_diloco_outer_rht": (c_i32, [c_p, c_i64, c_i64, c_i32, c_i64, c_f32, c_p, c_p, c_i32, c_f32, c_f32,
                                     c_f32, c_f32, c_i32, c_i32, c_p, c_i64, c_i64, c_u32, c_p]),
+    "ga_lowrank_chain": (c_i64, [c_i64, c_i32]),
+    "ga_lowrank_project": (c_i32, [c_p, c_i64, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_f32, c_i32, c_p,
+                                   c_p]),
+    "ga_lowrank_orthonormalize": (c_i32, [c_p, c_i64, c_i32, c_p, c_p]),
+    "ga_lowrank_backproject": (c_i32, [c_p, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_i32, c_p, c_p]),
+    "ga_diloco_outer_lowrank": (c_i32, [c_p, c_i64, c_p, c_p, c_p, c_p, c_f32, c_i32, c_p, c_i64, c_i64, c_p, c_i64,
+                                        c_f32, c_p, c_p, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_p]),
     "ga_topk_row_bytes": (c_i64, [c_i64, c_i32]),
     "ga_topk_encode": (c_i32, [c_i32, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_p]),
     "ga_diloco_outer_sparse": (c_i32, [c_p, c_i64, c_i64, c_i32, c_i64, c_f32, c_p, c_p, c_i32, c_f32, c_f32,

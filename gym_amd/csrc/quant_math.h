@@ -34,9 +34,9 @@ struct QuantOuterParams {
     int first_step, nesterov;
 };
 
-__device__ __forceinline__ float quant_outer_update(float acc, float& master, float& buf,
-                                                    const QuantOuterParams& op) {
-    float g = rn_div(acc, op.divisor);
+// The update from the pseudo-gradient g itself (lowrank.hip forms g without a division).
+__device__ __forceinline__ float outer_update_from_g(float g, float& master, float& buf,
+                                                     const QuantOuterParams& op) {
     if (op.weight_decay != 0.f) g = fmaf(op.weight_decay, master, g);
     if (op.momentum != 0.f) {
         if (op.first_step) buf = g;
@@ -45,6 +45,11 @@ __device__ __forceinline__ float quant_outer_update(float acc, float& master, fl
     }
     master = fmaf(-op.lr, g, master);
     return master;
+}
+
+__device__ __forceinline__ float quant_outer_update(float acc, float& master, float& buf,
+                                                    const QuantOuterParams& op) {
+    return outer_update_from_g(rn_div(acc, op.divisor), master, buf, op);
 }
 
 }  // namespace ga

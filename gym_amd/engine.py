@@ -736,6 +736,95 @@ class DiLoCoOuterTopK:
         self.first = False
 
 
+LOWRANK = "lowrank"  # outer_compression: rank-r PowerSGD factors (outer_rank, outer_lowrank_seed)
+
+
+class DiLoCoOuterLowRank:
+    """DiLoCo's outer step (SGD family) on low-rank (PowerSGD) pseudo-gradients, with
+    DiLoCoOuterQuant's call surface.
+
+    The one compressed exchange that is linear in the pseudo-gradient: every tensor with
+    ndim >= 2 and r (m + n) < m n (viewed d0 x numel / d0) is sent as the rank-r factors
+    P = M Q and B = M^T P^, summed over the nodes by two plain all-reduces whose bytes per
+    rank do not grow with the world size (plan.wire_bytes per step); every other tensor
+    rides the first all-reduce exactly, with ga_diloco_outer's arithmetic.  Four launches:
+    ga_lowrank_project, ga_lowrank_orthonormalize, ga_lowrank_backproject and
+    ga_diloco_outer_lowrank (decode fused into the outer update).  Every rank holds the
+    same factors after the all-reduces, so all nodes end bit-identical without a broadcast;
+    the results are NOT bit-identical between K nodes in one process and K processes (the
+    local sum is taken before the product in the first case, after it in the second).
+
+    Master and momentum are fp32 and REPLICATED on every process (8 B per parameter per
+    rank), Q (the decode factor and the next step's warm start, drawn from `seed` at first)
+    is replicated too.  error_feedback keeps a [K_local, n] fp32 residual: what rank r
+    dropped from a node's delta is added to its next one; without it that mass is lost, so
+    feedback is the intended use.  fp32 arenas only; no placement search, no masked (SPARTA
+    boundary) step."""
+
+    def __init__(self, coll: Collective, K_local, n, device, dtype, layout=None, rank=4, seed=0,
+                 error_feedback=False, lr=0.7, momentum=0.9, nesterov=True, dampening=0.0, weight_decay=0.0,
+                 placement=True):
+        from .lowrank import LowRankPlan
+        if layout is None:
+            raise ValueError("DiLoCoOuterLowRank: outer_compression='lowrank' needs the arena's layout (shapes and "
+                             "offsets of its tensors: build_outer_engine(..., layout=arena.layout)); fragments of a "
+                             "tensor table are not built")
+        if dtype != torch.float32:
+            raise ValueError(f"DiLoCoOuterLowRank: outer_compression='lowrank' needs an fp32 arena (bf16 rows are not "
+                             f"built); got {dtype}")
+        self.coll, self.K_local, self.n = coll, int(K_local), int(n)
+        self.K_total = coll.world * self.K_local
+        self.hp = dict(lr=lr, momentum=momentum, nesterov=nesterov, dampening=dampening, weight_decay=weight_decay)
+        self.shard, self.per, self.dtype = False, self.n, dtype
+        self.plan = LowRankPlan(layout.shapes, layout.offsets, self.n, rank).to(device)
+        self.rank, self.seed = self.plan.rank, seed
+        self._state = torch.zeros((2 if momentum != 0 else 1) * self.n, device=device, dtype=torch.float32)
+        self.master = self._state[:self.n]
+        self.mom = self._state[self.n:] if momentum != 0 else None
+        self.residual = (torch.zeros(self.K_local, self.n, device=device, dtype=torch.float32)
+                         if error_feedback else None)
+        self.A = torch.zeros(max(self.plan.a_len, 1), device=device, dtype=torch.float32)
+        # B of the last step; Q = B / q_div is the decode factor and the next warm start
+        self.B = self.plan.warm_start(seed).to(device)
+        self.q_div = 1.0
+        self.wire_bytes = self.plan.wire_bytes
+        # `placement` is taken as on every outer engine (build_outer_engine passes it); there is no search
+        self.placement = {"placed": False, "why": "no search for the low-rank outer step"}
+        self.relocate_replicas = None  # accepted as on DiLoCoOuter; the set stays where it is
+        self.first = True
+        self.launch_elems = []  # elements per ga_diloco_outer_lowrank launch of the last step
+
+    def init_master(self, params_flat):
+        """master <- the node's initial parameters (diloco.py:81-82); no error carried over,
+        the warm start drawn again."""
+        self.master.copy_(params_flat[:self.n])
+        if self.residual is not None:
+            self.residual.zero_()
+        self.B.copy_(self.plan.warm_start(self.seed))
+        self.q_div = 1.0
+        self.first = True
+
+    def __call__(self, reps, sparse_mask=None):
+        if sparse_mask is not None:
+            raise ValueError("DiLoCoOuterLowRank: no one-pass masked outer step; run Sparta and the outer step one "
+                             "after the other")
+        n, h, plan = self.n, self.hp, self.plan
+        rows = reps[:, :n]
+        ops.lowrank_project(plan, rows, self.master, self.residual, self.B, self.q_div, self.A)
+        if self.coll.exchange:
+            self.coll.all_reduce_(self.A)
+        ops.lowrank_orthonormalize(plan, self.A)
+        ops.lowrank_backproject(plan, rows, self.master, self.residual, self.A, self.B)
+        if self.coll.exchange:
+            self.coll.all_reduce_(self.B)
+        self.q_div = float(self.K_total)
+        ops.diloco_outer_lowrank(plan, self.A, self.B, self.q_div, rows, self.residual, self.master, self.mom,
+                                 self.K_total, h["lr"], h["momentum"], h["dampening"], h["weight_decay"],
+                                 h["nesterov"], self.first)
+        self.launch_elems = [n]
+        self.first = False
+
+
 class DiLoCoOuterStream:
     """Streaming DiLoCo's outer step (SGD family) for one fragment: the exchange
     is sent at one step and its result merged `delay` inner steps later, mixed

@@ -477,6 +477,90 @@ def diloco_outer_rht(payload, master, mom, dst, n, bits, divisor, lr, momentum, 
                  extra=(_rotation_seed("diloco_outer_rht", seed),))
 
 
+def lowrank_chain(length, backproject=False):
+    """L of the low-rank products' error bound for a band that walks `length` elements
+    (ga_lowrank_chain: columns of the projection, rows of the back-projection)."""
+    return int(lib().ga_lowrank_chain(int(length), int(bool(backproject))))
+
+
+def _lowrank_rows(who, plan, x, master, residual):
+    """(x as [K, ld], K, ld_x, residual as [K, ld] or None, ld_r) of a low-rank launch, every
+    buffer checked against the plan (the kernels trust the plan's offsets)."""
+    x2 = _as2d(x)
+    r2 = _as2d(residual) if residual is not None else None
+    _gpu(x2, master, r2)
+    if plan.device is None or plan.device != x2.device:
+        raise ValueError(f"{who}: the plan's tables are not on {x2.device} (LowRankPlan.to)")
+    K, ldx = _rows_ld(x2)
+    if x2.shape[1] < plan.n or master.numel() < plan.n or (r2 is not None and r2.shape[1] < plan.n):
+        raise ValueError(f"{who}: buffers shorter than the plan's {plan.n} elements")
+    for t in (x2, master, r2):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"{who}: fp32 buffers only (bf16 rows are not built)")
+    if not master.is_contiguous() or x2.stride(1) != 1:
+        raise ValueError(f"{who}: master and the rows must be contiguous")
+    ldr = 0
+    if r2 is not None:
+        if r2.shape[0] != K or r2.stride(1) != 1:
+            raise ValueError(f"{who}: the residual is a contiguous set with one row per row of x")
+        ldr = _rows_ld(r2)[1]
+    return x2, K, ldx, r2, ldr
+
+
+def _lowrank_factor(who, name, t, need):
+    _gpu(t)
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < need:
+        raise ValueError(f"{who}: {name} must be a contiguous float32 tensor of at least {need} elements")
+
+
+def lowrank_project(plan, x, master, residual, q, q_div, a):
+    """a <- the projections P_t = sum_k ((master - x_k) + e_k) (q_t / q_div) of the compressed
+    tensors of `plan` and the ascending fp32 row sums of its dense segments (ga_lowrank_project)."""
+    x2, K, ldx, r2, ldr = _lowrank_rows("lowrank_project", plan, x, master, residual)
+    _lowrank_factor("lowrank_project", "q", q, plan.b_len)
+    _lowrank_factor("lowrank_project", "a", a, plan.a_len)
+    check(lib().ga_lowrank_project(_p(plan.d_project), len(plan.project_jobs), _p(plan.d_tensors),
+                                   _p(plan.d_segments), _p(x2), K, ldx, _p(master), _p(r2), ldr, _p(q),
+                                   float(q_div), plan.rank, _p(a), _stream()), "ga_lowrank_project")
+
+
+def lowrank_orthonormalize(plan, a):
+    """Every P_t of `a` orthonormalised in place, column by column with two projections;
+    zero and noise-level columns become exactly 0 (ga_lowrank_orthonormalize)."""
+    _lowrank_factor("lowrank_orthonormalize", "a", a, plan.a_len)
+    if plan.device is None or plan.device != a.device:
+        raise ValueError(f"lowrank_orthonormalize: the plan's tables are not on {a.device} (LowRankPlan.to)")
+    check(lib().ga_lowrank_orthonormalize(_p(plan.d_tensors), len(plan.tensors), plan.rank, _p(a), _stream()),
+          "ga_lowrank_orthonormalize")
+
+
+def lowrank_backproject(plan, x, master, residual, a, b):
+    """b <- B_t = sum_k ((master - x_k) + e_k)^T P^_t of the compressed tensors (ga_lowrank_backproject)."""
+    x2, K, ldx, r2, ldr = _lowrank_rows("lowrank_backproject", plan, x, master, residual)
+    _lowrank_factor("lowrank_backproject", "a", a, plan.a_len)
+    _lowrank_factor("lowrank_backproject", "b", b, plan.b_len)
+    check(lib().ga_lowrank_backproject(_p(plan.d_backproject), len(plan.backproject_jobs), _p(plan.d_tensors),
+                                       _p(x2), K, ldx, _p(master), _p(r2), ldr, _p(a), plan.rank, _p(b), _stream()),
+          "ga_lowrank_backproject")
+
+
+def diloco_outer_lowrank(plan, a, q, q_div, x, residual, master, mom, divisor, lr, momentum, dampening, weight_decay,
+                         nesterov, first_step):
+    """The DiLoCo outer step on g = P^ (q / q_div)^T (compressed tensors; residual <- M_k - g)
+    and g = master - S / divisor (dense segments, S from `a`): master / mom (fp32) updated as
+    by diloco_outer, every row of x <- the new master (ga_diloco_outer_lowrank)."""
+    x2, K, ldx, r2, ldr = _lowrank_rows("diloco_outer_lowrank", plan, x, master, residual)
+    _lowrank_factor("diloco_outer_lowrank", "a", a, plan.a_len)
+    _lowrank_factor("diloco_outer_lowrank", "q", q, plan.b_len)
+    if mom is not None:
+        _lowrank_factor("diloco_outer_lowrank", "mom", mom, plan.n)
+    check(lib().ga_diloco_outer_lowrank(_p(plan.d_outer), len(plan.outer_jobs), _p(plan.d_tensors),
+                                        _p(plan.d_segments), _p(a), _p(q), float(q_div), plan.rank, _p(x2), K, ldx,
+                                        _p(r2), ldr, float(divisor), _p(master), _p(mom), int(bool(first_step)),
+                                        float(lr), float(momentum), float(dampening), float(weight_decay),
+                                        int(bool(nesterov)), _stream()), "ga_diloco_outer_lowrank")
+
+
 def topk_row_bytes(n, k):
     """Bytes of one top-k payload row of n elements (ga_topk_row_bytes: 4096-element chunks,
     k fp32 values then k uint16 indices per chunk, rounded up to 16)."""

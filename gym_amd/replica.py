@@ -49,8 +49,8 @@ from torch.utils.data import DataLoader
 from . import ops
 from .arena import ReplicaArena
 from .comm import Collective
-from .engine import (DiLoCoOuter, DiLoCoOuterIslands, DiLoCoOuterQuant, DiLoCoOuterTopK, FragmentedOuter, MeanReduce,
-                     demo_codec, node_mean)
+from .engine import (DiLoCoOuter, DiLoCoOuterIslands, DiLoCoOuterLowRank, DiLoCoOuterQuant, DiLoCoOuterTopK,
+                     FragmentedOuter, MeanReduce, demo_codec, node_mean)
 from .fused_optim import build_fused
 from .strategy.demo import DeMoStrategy
 from .strategy.diloco import DiLoCoStrategy, build_outer_engine, build_streaming_outer, streaming_options
@@ -165,7 +165,8 @@ class ReplicaRunner:
                     self.outer = build_streaming_outer(s, s.outer_optim_spec, self.coll, self.K, ld, dev, dt,
                                                        self.ra.layout.offsets, opts)
                 else:
-                    self.outer = build_outer_engine(s, s.outer_optim_spec, self.coll, self.K, ld, dev, dt)
+                    self.outer = build_outer_engine(s, s.outer_optim_spec, self.coll, self.K, ld, dev, dt,
+                                                    layout=self.ra.layout)
                 self.outer.init_master(self.ra.flat_set[0])
                 self.outer_optimizer = getattr(self.outer, "optimizer", None)
                 # the step may move the replica set itself (every model re-pointed)
@@ -199,7 +200,7 @@ class ReplicaRunner:
                 self.fuse = bool(s.fuse_boundary and not self.sparta.philox and self.sparta.plan is None
                                  and not self.coll.exchange and isinstance(self.outer, DiLoCoOuter))
                 s.fuse_boundary = self.fuse
-                if isinstance(self.outer, (DiLoCoOuter, DiLoCoOuterQuant, DiLoCoOuterTopK)):
+                if isinstance(self.outer, (DiLoCoOuter, DiLoCoOuterQuant, DiLoCoOuterTopK, DiLoCoOuterLowRank)):
                     s.engine = self.outer  # Strategy.placement_records reads the outer step's record there
         # the strategy's LR schedule on every optimizer (strategy.py:75-112)
         for o in (self.optim.opts if isinstance(self.optim, _PerNodeOptim) else [self.optim]):

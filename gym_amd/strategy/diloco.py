@@ -49,6 +49,17 @@ so feedback is the intended use.  outer_topk is ignored for any other compressio
 Same restrictions as the quantised step (plain SGD outer optimizer, no delay / mix);
 it composes with num_fragments (chunks restart at each fragment's start).
 
+outer_compression="lowrank" sends rank-r PowerSGD factors instead (engine.DiLoCoOuterLowRank,
+DESIGN §3 "Low-rank outer step"): every tensor with ndim >= 2 and r (m + n) < m n, viewed as
+d0 x numel / d0, goes as P = M Q and B = M^T P^ through two plain all-reduces, everything else
+exactly through the first of them.  The format is linear, so the bytes per rank do not grow
+with the world size.  outer_rank=r (default 4, 1..32) and outer_lowrank_seed (default 0, the
+same on every rank: the first warm-start Q) are ignored for any other compression.
+outer_error_feedback=True keeps what rank r dropped from a node's delta for its next outer
+step; without it that mass is lost, so feedback is the intended use.  Plain SGD outer
+optimizer, fp32 arenas, no delay / mix, num_fragments=1, no islands.  Results are not
+bit-identical between K nodes in one process and K processes.
+
 Streaming DiLoCo (DESIGN §3 "Streaming outer step"): num_fragments=F cuts the arena
 into F fragments that take their outer steps on staggered schedules (an outer event
 moves about n / F elements), outer_delay=tau applies an exchange's result tau inner
@@ -62,9 +73,10 @@ from typing import Optional, Union
 import torch
 
 from .. import ops
-from ..engine import (MX_FORMATS, QUANT_BITS, RHT_FORMATS, DiLoCoOuter, DiLoCoOuterAdam, DiLoCoOuterMX,
-                      DiLoCoOuterQuant, DiLoCoOuterRHT, DiLoCoOuterStream, DiLoCoOuterTopK, FragmentedOuter, TorchOuter,
-                      check_rotation_seed, check_topk, fragment_bounds)
+from ..engine import (LOWRANK, MX_FORMATS, QUANT_BITS, RHT_FORMATS, DiLoCoOuter, DiLoCoOuterAdam, DiLoCoOuterLowRank,
+                      DiLoCoOuterMX, DiLoCoOuterQuant, DiLoCoOuterRHT, DiLoCoOuterStream, DiLoCoOuterTopK,
+                      FragmentedOuter, TorchOuter, check_rotation_seed, check_topk, fragment_bounds)
+from ..lowrank import check_lowrank_seed, check_rank
 from .communicate_optimize_strategy import CommunicationModule
 from .optim import OptimSpec, ensure_optim_spec
 from .strategy import Strategy, build_inner_optimizer, clip_and_step
@@ -116,18 +128,19 @@ def fused_adam_hparams(spec: OptimSpec):
                 weight_decay=float(weight_decay), decoupled=decoupled)
 
 
-def check_outer_compression(compression, spec, topk=32, rotation_seed=0):
+def check_outer_compression(compression, spec, topk=32, rotation_seed=0, rank=4, lowrank_seed=0):
     """The bit width of outer_compression (None: off; TOPK itself for "topk", after
     outer_topk = `topk` was checked) for outer OptimSpec `spec`; ValueError for an
     unknown string or an outer optimizer without a compressed step.  outer_topk is
     not looked at for any other compression, outer_rotation_seed = `rotation_seed` only
-    for the rotated formats."""
+    for the rotated formats, outer_rank = `rank` and outer_lowrank_seed = `lowrank_seed` only
+    for "lowrank" (LOWRANK itself is returned for it)."""
     if compression is None:
         return None
     formats = {**QUANT_BITS, **MX_FORMATS, **RHT_FORMATS}
-    if not isinstance(compression, str) or (compression != TOPK and compression not in formats):
+    if not isinstance(compression, str) or (compression not in (TOPK, LOWRANK) and compression not in formats):
         raise ValueError(f"outer_compression={compression!r}: expected None, "
-                         + " or ".join(map(repr, [*formats, TOPK])))
+                         + " or ".join(map(repr, [*formats, TOPK, LOWRANK])))
     if fused_sgd_hparams(spec) is None:
         raise ValueError(f"outer_compression={compression!r} needs a plain torch.optim.SGD outer optimizer (the "
                          f"quantised and sparse outer steps have no other update); got {spec.cls.__name__} with "
@@ -135,6 +148,10 @@ def check_outer_compression(compression, spec, topk=32, rotation_seed=0):
     if compression == TOPK:
         check_topk(topk)
         return TOPK
+    if compression == LOWRANK:
+        check_rank(rank)
+        check_lowrank_seed(lowrank_seed)
+        return LOWRANK
     if compression in RHT_FORMATS:
         check_rotation_seed(rotation_seed)
     return formats[compression]
@@ -162,6 +179,9 @@ def check_streaming(num_fragments, outer_delay, outer_mix, H, spec, compression)
         if compression is not None:
             raise ValueError(f"outer_delay={outer_delay!r} / outer_mix={outer_mix!r} cannot be combined with "
                              f"outer_compression={compression!r} (no delayed quantised step)")
+    if compression == LOWRANK and num_fragments != 1:
+        raise ValueError(f"num_fragments={num_fragments!r} cannot be combined with outer_compression={LOWRANK!r} "
+                         f"(fragments of a tensor table are not built)")
     return int(num_fragments), int(outer_delay), float(outer_mix)
 
 
@@ -177,20 +197,28 @@ def streaming_options(strategy, spec):
     return None if opts == (1, 0, 0.0) else opts
 
 
-def build_outer_engine(strategy, spec, coll, K_local, n, device, dtype, placement=None):
+def build_outer_engine(strategy, spec, coll, K_local, n, device, dtype, placement=None, layout=None):
     """The outer step of outer OptimSpec `spec` over a [K_local, n] set:
     DiLoCoOuter for plain SGD, DiLoCoOuterAdam for Adam / AdamW unless the
     strategy was built with fused_outer=False (the A/B switch against torch's
     optimizer; SGD specs are always fused), TorchOuter (torch's optimizer on an
     fp32 master) for every other spec.  With outer_compression set:
     DiLoCoOuterQuant ("int8" / "int4"), DiLoCoOuterMX ("mxfp8" / "mxfp4"), DiLoCoOuterRHT ("rht-int8" /
-    "rht-int4", seed = outer_rotation_seed) or DiLoCoOuterTopK ("topk", k = outer_topk) for plain SGD, ValueError for anything else.  placement: the engine's placement
+    "rht-int4", seed = outer_rotation_seed), DiLoCoOuterTopK ("topk", k = outer_topk) or DiLoCoOuterLowRank
+    ("lowrank", outer_rank, outer_lowrank_seed; it needs `layout`, the arena's ArenaLayout, and an fp32
+    arena) for plain SGD, ValueError for anything else.  placement: the engine's placement
     option, None for the strategy's."""
     placement = strategy.placement_opt if placement is None else placement
     bits = check_outer_compression(strategy.kwargs.get("outer_compression"), spec,
                                    strategy.kwargs.get("outer_topk", 32),
-                                   strategy.kwargs.get("outer_rotation_seed", 0))
+                                   strategy.kwargs.get("outer_rotation_seed", 0),
+                                   strategy.kwargs.get("outer_rank", 4), strategy.kwargs.get("outer_lowrank_seed", 0))
     hp = fused_sgd_hparams(spec)
+    if bits == LOWRANK:  # the engine refuses a missing layout and a bf16 arena
+        return DiLoCoOuterLowRank(coll, K_local, n, device, dtype, layout=layout, placement=placement,
+                                  rank=strategy.kwargs.get("outer_rank", 4),
+                                  seed=strategy.kwargs.get("outer_lowrank_seed", 0),
+                                  error_feedback=bool(strategy.kwargs.get("outer_error_feedback", False)), **hp)
     if bits == TOPK:
         return DiLoCoOuterTopK(coll, K_local, n, device, dtype, k=strategy.kwargs.get("outer_topk", 32),
                                placement=placement,
@@ -249,7 +277,8 @@ def start_outer(holder, strategy, spec, arena):
         outer = build_streaming_outer(strategy, spec, strategy.coll, 1, arena.n, arena.device, arena.dtype,
                                       arena.layout.offsets, opts)
     else:
-        outer = build_outer_engine(strategy, spec, strategy.coll, 1, arena.n, arena.device, arena.dtype)
+        outer = build_outer_engine(strategy, spec, strategy.coll, 1, arena.n, arena.device, arena.dtype,
+                                   layout=arena.layout)
     outer.init_master(arena.flat)
     holder.outer_optimizer = None
     if isinstance(outer, TorchOuter):
@@ -293,18 +322,22 @@ class DiLoCoStrategy(Strategy):
                  outer_optim_spec: Optional[Union[str, OptimSpec]] = None, H: int = 100,
                  outer_compression: Optional[str] = None, outer_error_feedback: bool = False,
                  num_fragments: int = 1, outer_delay: int = 0, outer_mix: float = 0.0, outer_topk: int = 32,
-                 outer_rotation_seed: int = 0, **kwargs):
+                 outer_rotation_seed: int = 0, outer_rank: int = 4, outer_lowrank_seed: int = 0, **kwargs):
         self.inner_optim_spec = ensure_optim_spec(optim_spec, OptimSpec(torch.optim.AdamW))
         self.outer_optim_spec = ensure_optim_spec(outer_optim_spec, default_outer_spec())
         self.H = H
         check_rotation_seed(outer_rotation_seed)
-        check_outer_compression(outer_compression, self.outer_optim_spec, outer_topk, outer_rotation_seed)
+        check_rank(outer_rank)
+        check_lowrank_seed(outer_lowrank_seed)
+        check_outer_compression(outer_compression, self.outer_optim_spec, outer_topk, outer_rotation_seed, outer_rank,
+                                outer_lowrank_seed)
         num_fragments, outer_delay, outer_mix = check_streaming(num_fragments, outer_delay, outer_mix, H,
                                                                 self.outer_optim_spec, outer_compression)
         # all reach build_outer_engine / build_streaming_outer through self.kwargs, as fused_outer does
         super().__init__(outer_compression=outer_compression, outer_error_feedback=bool(outer_error_feedback),
                          num_fragments=num_fragments, outer_delay=outer_delay, outer_mix=outer_mix,
-                         outer_topk=outer_topk, outer_rotation_seed=outer_rotation_seed, **kwargs)
+                         outer_topk=outer_topk, outer_rotation_seed=outer_rotation_seed, outer_rank=outer_rank,
+                         outer_lowrank_seed=outer_lowrank_seed, **kwargs)
 
     def _init_node(self, model, rank, num_nodes):
         super()._init_node(model, rank, num_nodes)

@@ -26,11 +26,16 @@ outer step has no masked form: the two modules run in sequence and
 fuse_boundary reads False.  outer_compression="topk" with outer_topk= (default 32)
 sends the k largest entries of every 4096-element chunk instead, with the same
 restrictions; "rht-int8" | "rht-int4" with outer_rotation_seed= (default 0) send the
-integer payload quantised after a Hadamard rotation of every block.
+integer payload quantised after a Hadamard rotation of every block;
+outer_compression="lowrank" with outer_rank= (default 4) and outer_lowrank_seed= (default 0)
+sends rank-r PowerSGD factors through two all-reduces (engine.DiLoCoOuterLowRank; fp32 arenas,
+feedback is the intended use).  A boundary step runs the listed or masked average, then that
+step: there is no masked one-pass form.
 """
 from typing import Optional, Union
 
 from ..engine import check_rotation_seed
+from ..lowrank import check_lowrank_seed, check_rank
 from .communicate_optimize_strategy import CommunicateOptimizeStrategy
 from .diloco import DiLoCoCommunicator, check_outer_compression
 from .optim import OptimSpec
@@ -41,15 +46,20 @@ class SPARTADiLoCoStrategy(CommunicateOptimizeStrategy):
     def __init__(self, inner_optim: Optional[Union[str, OptimSpec]] = None,
                  outer_optim: Optional[Union[str, OptimSpec]] = None, p_sparta: float = 0.005, H: int = 100,
                  mask_source="torch", fuse_boundary=True, outer_compression: Optional[str] = None,
-                 outer_error_feedback: bool = False, outer_topk: int = 32, outer_rotation_seed: int = 0, **kwargs):
+                 outer_error_feedback: bool = False, outer_topk: int = 32, outer_rotation_seed: int = 0,
+                 outer_rank: int = 4, outer_lowrank_seed: int = 0, **kwargs):
         index_selector = RandomIndexSelector(p_sparta, mask_source=mask_source)
         sparse_comm = SparseCommunicator(index_selector)
         diloco_comm = DiLoCoCommunicator(H=H, outer_optim=outer_optim)
         check_rotation_seed(outer_rotation_seed)
-        check_outer_compression(outer_compression, diloco_comm.outer_optim_spec, outer_topk, outer_rotation_seed)
+        check_rank(outer_rank)
+        check_lowrank_seed(outer_lowrank_seed)
+        check_outer_compression(outer_compression, diloco_comm.outer_optim_spec, outer_topk, outer_rotation_seed,
+                                outer_rank, outer_lowrank_seed)
         super().__init__(communication_modules=[sparse_comm, diloco_comm], inner_optim=inner_optim,
                          outer_compression=outer_compression, outer_error_feedback=bool(outer_error_feedback),
-                         outer_topk=outer_topk, outer_rotation_seed=outer_rotation_seed, **kwargs)
+                         outer_topk=outer_topk, outer_rotation_seed=outer_rotation_seed, outer_rank=outer_rank,
+                         outer_lowrank_seed=outer_lowrank_seed, **kwargs)
         self.index_selector = index_selector
         self.p_sparta = p_sparta
         self.H = H

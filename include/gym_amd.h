@@ -483,6 +483,76 @@ GA_API int ga_diloco_outer_rht(const void* payload, int64_t S, int64_t ld_q_byte
                                float momentum, float dampening, float weight_decay, int nesterov, int dtype,
                                void* dst, int64_t K_out, int64_t ld_dst, uint32_t seed, hipStream_t stream);
 
+/* ---- DiLoCo outer step on low-rank (PowerSGD) pseudo-gradients ---------- */
+
+/*
+ * The one compressed outer step that is LINEAR in the pseudo-gradient (Vogels et al. 2019;
+ * no reference counterpart): the factors of different nodes add, so they ride two plain
+ * all-reduces whose bytes per rank do not depend on the world size.  fp32 arenas only.
+ *
+ * Plan (host-built once from the arena's shapes and offsets, all tables in device memory):
+ *   tensors   int64 rows {off, m, n, kind, poff, qoff}.  A tensor of shape (d0, ..) at arena
+ *             offset off is the row-major m x n matrix d0 x numel / d0; kind = 1 (compressed)
+ *             iff ndim >= 2 and r (m + n) < m n, else 0 (dense).  P_t = A[poff .. poff + m r)
+ *             and Q_t = Q[qoff .. qoff + n r) are row-major with r columns.
+ *   segments  int64 rows {off, len, aoff}: a run of dense elements (dense tensors, padding)
+ *             and the start of its sums in A; off and aoff are multiples of 4.
+ *   jobs      int32 rows {id, band, tile, 0}, one workgroup each.  id >= 0: tensor id (project:
+ *             rows 32 band ..; back-project: columns 32 band ..; outer: rows 32 band .., columns
+ *             128 tile ..); id < 0: elements 4096 band .. of segment -1 - id.
+ * The entry points cannot check device tables: every offset in them must lie inside the
+ * buffers passed (gym_amd.lowrank.LowRankPlan builds and gym_amd.ops checks them).
+ *
+ * One outer step, K local rows x_k, K_total nodes in all, Q_t = q[..] / q_div (true division;
+ * the warm start: randn with q_div = 1 at first, afterwards the last step's B with q_div =
+ * K_total).  Node k's pseudo-gradient is M_k = (master - x_k) + e_k in fp32 (e_k = 0 without
+ * a residual); every sum over local nodes is fp32, ascending k from 0.
+ *   1 ga_lowrank_project         A: P_t = sum_k M_k Q_t on compressed tensors, the sum of the
+ *                                x_k on dense segments.  [all-reduce SUM of A]
+ *   2 ga_lowrank_orthonormalize  every P_t in place: columns c = 0 .. r-1 in order; n0 = |p_c|^2;
+ *                                twice: d_b = p_c . p_b for all b < c, then p_c -= sum_b d_b p_b
+ *                                (ascending b); n2 = |p_c|^2; the column is set to exactly 0 if
+ *                                !(n2 > 0) or n2 <= 2^-40 n0, else p_c = p_c / sqrt(n2).  No
+ *                                epsilon; an all-zero P stays zero.  The second projection keeps
+ *                                a noise-level column orthogonal on rank-deficient input.
+ *   3 ga_lowrank_backproject     B_t = sum_k M_k^T P^_t  (n x r).  [all-reduce SUM of B]
+ *   4 ga_diloco_outer_lowrank    with Q_t = B_t / K_total: compressed elements g[i,j] =
+ *                                sum_c P^[i,c] Q[j,c] (fmaf chain from 0, ascending c); with a
+ *                                residual e_k[i,j] <- M_k[i,j] - g[i,j] on compressed tensors
+ *                                (M_k from the step's inputs); dense elements g = master -
+ *                                S / divisor exactly as ga_diloco_outer forms it.  Then
+ *                                ga_diloco_outer's update of master / mom, every row of x <- the
+ *                                new master.  Padding stays 0.
+ * No atomics; the same input gives the same bits.  Every rank holds the same A and B after the
+ * all-reduces, so all nodes end bit-identical.  Error: the products run on
+ * v_mfma_f32_32x32x2_f32 as fp32 multiply-add chains; with L = ga_lowrank_chain(n, 0) for the
+ * projection (ga_lowrank_chain(m, 1) for the back-projection), U = 2^-24 and K local rows,
+ * |P - P64| <= (L + 16 + K + 2) U (sum_k |master| + |x_k| + |e_k|) |Q| to first order.
+ */
+GA_API int64_t ga_lowrank_chain(int64_t len, int backproject);
+
+/* x: [K, ld_x] fp32 rows, master fp32, residual: [K, ld_r] fp32 or null, rank = r in 1..32. */
+GA_API int ga_lowrank_project(const int32_t* jobs, int64_t njobs, const int64_t* tensors,
+                              const int64_t* segments, const float* x, int64_t K, int64_t ld_x,
+                              const float* master, const float* residual, int64_t ld_r, const float* q,
+                              float q_div, int rank, float* a, hipStream_t stream);
+
+/* One workgroup per row of `tensors`; dense rows are skipped. */
+GA_API int ga_lowrank_orthonormalize(const int64_t* tensors, int64_t ntensors, int rank, float* a,
+                                     hipStream_t stream);
+
+GA_API int ga_lowrank_backproject(const int32_t* jobs, int64_t njobs, const int64_t* tensors, const float* x,
+                                  int64_t K, int64_t ld_x, const float* master, const float* residual,
+                                  int64_t ld_r, const float* a, int rank, float* b, hipStream_t stream);
+
+/* divisor = K_total.  x is read (with a residual) and every row overwritten with the new master. */
+GA_API int ga_diloco_outer_lowrank(const int32_t* jobs, int64_t njobs, const int64_t* tensors,
+                                   const int64_t* segments, const float* a, const float* q, float q_div,
+                                   int rank, float* x, int64_t K, int64_t ld_x, float* residual, int64_t ld_r,
+                                   float divisor, float* master, float* mom, int first_step, float lr,
+                                   float momentum, float dampening, float weight_decay, int nesterov,
+                                   hipStream_t stream);
+
 /* ---- DiLoCo outer step on top-k sparse pseudo-gradients ----------------- */
 
 /*
