@@ -129,6 +129,11 @@ SIGNATURES = {
                              c_f32, c_f32, c_f32, c_p, c_p]),
     "ga_sgd_step": (c_i32, [c_i32, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32,
                             c_p, c_p]),
+    "ga_muon_fields": (c_i32, []),
+    "ga_muon_prepare": (c_i32, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_f32, c_f32, c_i32, c_p, c_p]),
+    "ga_muon_scale": (c_i32, [c_p, c_i64, c_p, c_f32, c_p, c_p]),
+    "ga_muon_gemm": (c_i32, [c_i32, c_i32, c_p, c_i64, c_p, c_p, c_i32, c_f32, c_f32, c_p, c_p]),
+    "ga_muon_apply": (c_i32, [c_p, c_i64, c_p, c_p, c_p, c_i32, c_p, c_f32, c_f32, c_p]),
     "ga_replica_gram_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "ga_replica_gram_chain": (c_i32, []),
     "ga_replica_gram": (c_i32, [c_i32, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p]),

@@ -31,8 +31,11 @@ continues where it stopped.
 ArenaSGD is the same for OptimSpec(torch.optim.SGD, ...) (the "sgd" of
 OptimSpec.from_string, optim.py:24): one ga_sgd_step launch (read p, g, buf;
 write p, buf) with momentum, dampening, Nesterov and L2 weight decay, a
-per-parameter initialised flag where Adam has a step count.  build_fused picks
-the class for a spec; FUSED names both for the callers that step them.
+per-parameter initialised flag where Adam has a step count.  ArenaMuon is the
+"muon" spec (strategy.optim.MuonAdamW): Muon's Newton-Schulz iterations on the
+hidden matrices as grouped bf16 MFMA launches over job tables (ga_muon_*), an
+inner ArenaAdam on the rest.  build_fused picks the class for a spec; FUSED
+names them for the callers that step them.
 """
 import math
 import time
@@ -162,6 +165,9 @@ class _ArenaOptimizer(torch.optim.Optimizer):
             self._spans[k].append((p, o, n))
         for sp in self._spans:
             sp.sort(key=lambda t: t[1])
+        # an optimizer that owns only part of the arena (ArenaMuon's inner ArenaAdam) never
+        # steps a whole row: the other tensors belong to someone else
+        self._owns_arena = all(len(sp) == len(ar.params) for sp, ar in zip(self._spans, self.arenas))
         self._partials = ops.sumsq_partials(self.P.device, self.K)
         self._clip = torch.ones(2 * self.K, dtype=torch.float32, device=self.P.device)
 
@@ -191,7 +197,7 @@ class _ArenaOptimizer(torch.optim.Optimizer):
                     out[-1][1] = o + n
                 else:
                     out.append([o, o + n, key])
-            if len(out) == 1 and len(spans) == len(self._spans[k]):
+            if len(out) == 1 and len(spans) == len(self._spans[k]) and self._owns_arena:
                 out = [[0, self.ld, out[0][2]]]
             ranges.append([tuple(r) for r in out])
         return ranges
@@ -202,7 +208,9 @@ class _ArenaOptimizer(torch.optim.Optimizer):
         pass
 
     @torch.no_grad()
-    def step(self, closure=None, max_norm=None):
+    def step(self, closure=None, max_norm=None, clip=None):
+        """clip: the coefficients of a ga_grad_clip_coef the caller already ran over
+        the gradient set (ArenaMuon clips both of its parts by one norm)."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -213,8 +221,7 @@ class _ArenaOptimizer(torch.optim.Optimizer):
         if not any(ranges):  # no parameter has a gradient: torch's step does nothing
             return loss
         self._prepare()
-        clip = None
-        if max_norm:
+        if clip is None and max_norm:
             ops.grad_clip_coef(self.G, self.ld, max_norm, self._partials, self._clip)
             clip = self._clip
         whole = ranges[0]
@@ -427,7 +434,7 @@ class ArenaAdam(_ArenaOptimizer):
         are all present advances with one add; one that is partly present
         splits; groups that reach the same count become one again."""
         groups = self._groups
-        if len(groups) == 1 and all(m[0].grad is not None for m in groups[0][1]):
+        if self._owns_arena and len(groups) == 1 and all(m[0].grad is not None for m in groups[0][1]):
             groups[0][0] += 1  # every parameter present on one count: nothing per parameter
             return [[(0, self.ld, float(groups[0][0]))]] * self.K
         live = [[] for _ in range(self.K)]
@@ -616,17 +623,285 @@ class ArenaSGD(_ArenaOptimizer):
             self._bind_state(p)
 
 
-FUSED = (ArenaAdam, ArenaSGD)  # the inner optimizers whose step(max_norm=) clips on the device
+# the "muon" spec without a `fused` kwarg: ArenaMuon, which was 3.5-4.1x faster than the unfused
+# MuonAdamW in every alternated pair at K = 1 and K = 8 (profiles/inner_muon.txt); fused=False opts out
+MUON_FUSED_DEFAULT = True
+MUON_PLAN_CACHE = 8  # present sets whose device tables an ArenaMuon keeps (least recently used evicted)
 
 
-def build_fused(spec, params, arena, placement=True):
+def _round_up(x, m):
+    return (x + m - 1) // m * m
+
+
+class MuonPlan:
+    """The device tables of one Muon pass over a replica row (include/gym_amd.h,
+    "Muon inner step"), for the matrices `present` of `slots`: the matrix table,
+    the prepare / apply jobs (64 x 64 tiles of each parameter), and per macro-tile
+    class (128, or 64 for matrices whose short side fits one 64 tile) the jobs of
+    the symmetric products (tile column >= tile row) and of the update (every
+    tile).  slots: per Muon matrix (offset, rows, cols, tile, m_pad, n_pad, x,
+    xt0, xt1, a, b, ratio), the workspace offsets fixed for the arena layout
+    whichever matrices are present, so a matrix's padding only ever receives the
+    zeros its own products compute."""
+
+    def __init__(self, slots, present, device):
+        import struct
+        F = ops.muon_fields()
+        P = ops.MUON_PREP_TILE
+        mats, prep = [], []
+        sym, upd = {64: [], 128: []}, {64: [], 128: []}
+        for t, s in enumerate(slots[i] for i in present):
+            off, rows, cols, tile, m_pad, n_pad, x, xt0, xt1, a, b, ratio = s
+            job0 = len(prep)
+            prep += [(t, i, j, 0) for i in range(-(-rows // P)) for j in range(-(-cols // P))]
+            bits = struct.unpack("<I", struct.pack("<f", ratio))[0]
+            row = [off, rows, cols, m_pad, n_pad, x, xt0, xt1, a, b, int(rows > cols), job0, len(prep) - job0, bits]
+            mats.append(row + [0] * (F - len(row)))
+            mt, nt = m_pad // tile, n_pad // tile
+            sym[tile] += [(t, i, j, 0) for i in range(mt) for j in range(i, mt)]
+            upd[tile] += [(t, i, j, 0) for i in range(mt) for j in range(nt)]
+
+        def table(rows, dtype, width):
+            return torch.tensor(rows, dtype=dtype).reshape(-1, width).to(device)
+
+        self.nmats = len(mats)
+        self.mats = table(mats, torch.int64, F)
+        self.prep = table(prep, torch.int32, 4)
+        self.classes = [(T, table(sym[T], torch.int32, 4), table(upd[T], torch.int32, 4)) for T in (128, 64) if sym[T]]
+        self.partials = torch.zeros(max(len(prep), 1), dtype=torch.float32, device=device)
+        self.scale = torch.ones(max(len(mats), 1), dtype=torch.float32, device=device)
+
+
+class ArenaMuon(torch.optim.Optimizer):
+    """MuonAdamW (gym_amd.strategy.optim) over one node's ParamArena or a
+    ReplicaArena: torch.optim.Muon on the Muon matrices as grouped launches over
+    job tables (ga_muon_prepare, ga_muon_scale, 3 x ns_steps ga_muon_gemm,
+    ga_muon_apply: ~18 launches per replica where torch issues 15 GEMMs and as
+    many elementwise ops per matrix), and an inner ArenaAdam (AdamW) on every
+    other parameter.  param_groups[0] is Muon's group and param_groups[1] the
+    inner ArenaAdam's own, so a scheduler drives both learning rates.
+
+    muon_mask: a bool per parameter of one replica, in arena order
+    (strategy.optim.muon_matrix_mask).  The momentum is one fp32 [K, ld] set (4
+    bytes per arena element and replica, beside the inner ArenaAdam's two [K, ld]
+    moment sets: 12 bytes per arena element and replica in all); state[p]["momentum_buffer"] are views of
+    it, torch's state_dict layout.  The bf16 workspace (X, two copies of X^T, A and
+    B per matrix, padded to whole tiles) holds ONE replica's matrices: the K
+    replicas take their passes in turn.  step(max_norm=) clips both parts by one
+    coefficient per replica over its whole gradient row.  A matrix whose .grad is
+    None is skipped exactly (no decay, no buffer change): the job tables are built
+    for the present set and cached by it.  No host synchronisation in a step."""
+
+    def __init__(self, params, arena, muon_mask, lr=1e-3, weight_decay=0.1, momentum=0.95, nesterov=True,
+                 ns_coefficients=(3.4445, -4.775, 2.0315), eps=1e-7, ns_steps=5, adjust_lr_fn=None, adamw_lr=1e-3,
+                 adamw_betas=(0.9, 0.999), adamw_eps=1e-8, adamw_weight_decay=1e-2, placement=True):
+        if lr < 0.0 or adamw_lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}, {adamw_lr}")
+        if not 0.0 <= momentum < 1.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if len(ns_coefficients) != 3 or not 0 <= int(ns_steps) < 100:
+            raise ValueError("ArenaMuon: three ns_coefficients and 0 <= ns_steps < 100")
+        arenas = list(getattr(arena, "arenas", [arena]))
+        muon_mask = [bool(m) for m in muon_mask]
+        if any(len(ar.params) != len(muon_mask) for ar in arenas):
+            raise ValueError("ArenaMuon: muon_mask must hold a bool per parameter of a replica")
+        given = {id(p) for p in params}
+        mats = [[p for p, m in zip(ar.params, muon_mask) if m] for ar in arenas]
+        rest = [p for ar in arenas for p, m in zip(ar.params, muon_mask) if not m and p.requires_grad]
+        if not all(id(p) in given for ps in mats for p in ps) or not all(id(p) in given for p in rest):
+            raise ValueError("ArenaMuon: every parameter must live in the arena")
+        if not mats[0]:
+            raise ValueError("ArenaMuon: no Muon matrix selected")
+        self.adam = ArenaAdam(rest, arena, lr=adamw_lr, betas=adamw_betas, eps=adamw_eps,
+                              weight_decay=adamw_weight_decay, decoupled=True, placement=placement) if rest else None
+        group = dict(params=[p for ps in mats for p in ps], lr=lr, weight_decay=weight_decay, momentum=momentum,
+                     nesterov=bool(nesterov), ns_coefficients=tuple(ns_coefficients), eps=eps, ns_steps=int(ns_steps),
+                     adjust_lr_fn=adjust_lr_fn)
+        super().__init__([group] + ([self.adam.param_groups[0]] if self.adam else []), {})
+        self.arenas, self._arena = arenas, arena
+        self.K, self.ld = self.P.shape
+        self.muon_mask = muon_mask
+        self._mats = mats
+        layout = arenas[0].layout
+        self._slots, ws = [], 0
+        for i, m in enumerate(muon_mask):
+            if not m:
+                continue
+            shape = layout.shapes[i]
+            if len(shape) != 2:
+                raise ValueError(f"ArenaMuon: a Muon parameter must be 2-D, got {shape}")
+            rows, cols = shape
+            tile = 64 if min(rows, cols) <= 64 else 128
+            m_pad, n_pad = _round_up(min(rows, cols), tile), _round_up(max(rows, cols), tile)
+            x, xt0, xt1 = ws, ws + m_pad * n_pad, ws + 2 * m_pad * n_pad
+            a, b = ws + 3 * m_pad * n_pad, ws + 3 * m_pad * n_pad + m_pad * m_pad
+            ws += 3 * m_pad * n_pad + 2 * m_pad * m_pad
+            self._slots.append((layout.offsets[i], rows, cols, tile, m_pad, n_pad, x, xt0, xt1, a, b,
+                                self._ratio(adjust_lr_fn, rows, cols)))
+        dev = self.P.device
+        self.workspace = torch.zeros(ws, dtype=torch.bfloat16, device=dev)
+        self._B = torch.zeros_like(self.P, dtype=torch.float32)
+        self._plans = {}  # present matrices (indices into _slots) -> MuonPlan
+        self._partials = ops.sumsq_partials(dev, self.K)
+        self._clip = torch.ones(2 * self.K, dtype=torch.float32, device=dev)
+        if self.adam is not None:  # one state dict: torch's per-parameter entries of both parts
+            self.state.update(self.adam.state)
+            self.adam.state = self.state
+        self._bind_state()
+        self.placement = self.adam.placement if self.adam else None
+
+    @staticmethod
+    def _ratio(adjust_lr_fn, rows, cols):
+        """adjusted_lr / lr (torch/optim/_muon.py _adjust_lr)."""
+        if adjust_lr_fn is None or adjust_lr_fn == "original":
+            return math.sqrt(max(1, rows / cols))
+        if adjust_lr_fn == "match_rms_adamw":
+            return 0.2 * math.sqrt(max(rows, cols))
+        return 1.0
+
+    P = _ArenaOptimizer.P
+    G = _ArenaOptimizer.G
+
+    @property
+    def B(self):
+        """The momentum buffer [K, ld] (the Muon matrices' spans are used)."""
+        return self._B
+
+    def _bind_state(self):
+        for k, ps in enumerate(self._mats):
+            for p, s in zip(ps, self._slots):
+                self.state[p] = {"momentum_buffer": self._B[k, s[0]:s[0] + s[1] * s[2]].view(p.shape)}
+
+    def state_dict(self):
+        sd = super().state_dict()  # a `step` tensor of its own per parameter (ArenaAdam.state_dict)
+        sd["state"] = {i: ({**st, "step": st["step"].clone()} if "step" in st else st)
+                       for i, st in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """An ArenaMuon or MuonAdamW state dict of the same parameters: the Muon
+        group's hyper-parameters are taken over and its momentum buffers copied
+        into the flat buffer (state[p] keeps pointing at its views; a matrix
+        without an entry starts from zero), the AdamW group goes through
+        ArenaAdam.load_state_dict.  torch's Optimizer.load_state_dict is not
+        used for the Muon group: it would re-point state[p] at loose tensors."""
+        groups, saved = state_dict["param_groups"], state_dict["state"]
+        mine = [len(g["params"]) for g in self.param_groups]
+        if [len(g["params"]) for g in groups] != mine:
+            raise ValueError(f"ArenaMuon.load_state_dict: parameter groups of {mine} parameters expected, got "
+                             f"{[len(g['params']) for g in groups]}")
+        with torch.no_grad():
+            self._B.zero_()
+            for p, i in zip(self.param_groups[0]["params"], groups[0]["params"]):
+                buf = saved.get(i, {}).get("momentum_buffer")
+                if buf is not None:
+                    self.state[p]["momentum_buffer"].copy_(buf)
+        self.param_groups[0].update({k: v for k, v in groups[0].items() if k != "params"})
+        if self.adam is not None:
+            ids = groups[1]["params"]
+            self.adam.load_state_dict({"state": {j: saved[i] for j, i in enumerate(ids) if i in saved},
+                                       "param_groups": [{**groups[1], "params": list(range(len(ids)))}]})
+            self.param_groups[1] = self.adam.param_groups[0]
+            self.state.update(self.adam.state)
+            self.adam.state = self.state
+
+    def _plan(self, present):
+        plan = self._plans.pop(present, None)
+        if plan is None:
+            plan = MuonPlan(self._slots, present, self.P.device)
+            while len(self._plans) >= MUON_PLAN_CACHE:  # the least recently used set goes
+                del self._plans[next(iter(self._plans))]
+        self._plans[present] = plan  # most recently used last
+        return plan
+
+    def _muon_pass(self, k, plan, clip):
+        g = self.param_groups[0]
+        lr, wd, mom, ns = float(g["lr"]), float(g["weight_decay"]), float(g["momentum"]), int(g["ns_steps"])
+        a, b, c = (float(v) for v in g["ns_coefficients"])
+        ws = self.workspace
+        ops.muon_prepare(plan.prep, plan.mats, self.G[k], self._B[k], ws, plan.partials, momentum=mom,
+                         one_m_momentum=1 - mom, nesterov=g["nesterov"], clip_coef=clip)
+        ops.muon_scale(plan.mats, plan.partials, g["eps"], plan.scale)
+        for it in range(ns):
+            first = plan.scale if it == 0 else None  # the first iteration carries the normalisation
+            for T, sym, _ in plan.classes:
+                ops.muon_gemm(ops.MUON_GRAM, T, sym, plan.mats, ws, 0, 0.0, 1.0, first)
+            for T, sym, _ in plan.classes:
+                ops.muon_gemm(ops.MUON_POLY, T, sym, plan.mats, ws, 0, b, c)
+            for T, _, upd in plan.classes:
+                ops.muon_gemm(ops.MUON_UPDATE, T, upd, plan.mats, ws, it & 1, a, 1.0, first)
+        ops.muon_apply(plan.prep, plan.mats, self.P[k], ws, ns & 1, lr=lr, wd_factor=1 - lr * wd,
+                       scale=plan.scale if ns == 0 else None)
+
+    @torch.no_grad()
+    def step(self, closure=None, max_norm=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for ar in self.arenas:
+            ar.sync_grads()
+        present = [tuple(i for i, p in enumerate(ps) if p.grad is not None) for ps in self._mats]
+        rest = self.adam is not None and any(p.grad is not None for p in self.adam.param_groups[0]["params"])
+        if not rest and not any(present):
+            return loss
+        clip = None
+        if max_norm:  # one coefficient per replica over its whole gradient row
+            ops.grad_clip_coef(self.G, self.ld, max_norm, self._partials, self._clip)
+            clip = self._clip
+        for k, here in enumerate(present):
+            if here:
+                self._muon_pass(k, self._plan(here), clip[2 * k:2 * k + 2] if clip is not None else None)
+        if rest:
+            self.adam.step(clip=clip)
+            self.placement = self.adam.placement
+        return loss
+
+
+def fusable_muon(spec_cls, kwargs, arena):
+    """True when OptimSpec(spec_cls, **kwargs) can run as ArenaMuon on this arena:
+    MuonAdamW on an fp32 arena with a gradient set, float learning rates."""
+    from .strategy.optim import MuonAdamW
+    if spec_cls is not MuonAdamW or not _fp32_arena(arena):
+        return False
+    kw = dict(kwargs or {})
+    return not any(isinstance(kw.get(k), torch.Tensor) for k in ("lr", "adamw_lr"))
+
+
+FUSED = (ArenaAdam, ArenaSGD, ArenaMuon)  # the inner optimizers whose step(max_norm=) clips on the device
+
+
+def build_fused(spec, params, arena, placement=True, models=None):
     """The fused inner optimizer of OptimSpec `spec` over `arena` (ArenaAdam for
-    torch's AdamW / Adam, ArenaSGD for torch's SGD), or None when the spec stays
-    on torch: another optimizer or option, a bf16 arena, or GA_FUSED_OPTIM=0."""
+    torch's AdamW / Adam, ArenaSGD for torch's SGD, ArenaMuon for MuonAdamW with
+    `fused=True` -- MUON_FUSED_DEFAULT without the kwarg), or None when the spec
+    stays on torch: another optimizer or option, a bf16 arena, or
+    GA_FUSED_OPTIM=0.  models: the arena's modules (one per replica), from which
+    a MuonAdamW spec selects its matrices."""
     import os
     if os.environ.get("GA_FUSED_OPTIM", "1") == "0":
         return None
     kw = spec.kwargs or {}
+    if fusable_muon(spec.cls, kw, arena):
+        fused = kw.get("fused")
+        if not (MUON_FUSED_DEFAULT if fused is None else fused):
+            return None
+        from .strategy.optim import muon_matrix_mask
+        mask = kw.get("muon_mask")
+        if mask is None:
+            if not models:
+                return None
+            mask = muon_matrix_mask(models[0], kw.get("muon_exclude", ("lm_head",)), kw.get("muon_params"))
+        if not any(mask):
+            return None
+        opt = ArenaMuon(list(params), arena, mask, placement=placement,
+                        **{k: v for k, v in kw.items() if k not in ("muon_mask", "muon_exclude", "muon_params",
+                                                                    "fused")})
+        names = [n for n, _ in models[0].named_parameters()] if models else [str(i) for i in range(len(mask))]
+        opt.muon_names = [n for n, m in zip(names, mask) if m]
+        return opt
     if fusable(spec.cls, kw, arena):
         kw = {k: v for k, v in kw.items() if k in ("lr", "betas", "eps", "weight_decay")}
         return ArenaAdam(params, arena, decoupled=spec.cls is torch.optim.AdamW, placement=placement, **kw)

@@ -1085,4 +1085,74 @@ def sgd_step(param, grad, buf, *, neg_lr, momentum, one_m_dampening, weight_deca
                             int(bool(nesterov)), int(bool(first)), _p(clip_coef), _stream()), "ga_sgd_step")
 
 
+MUON_GRAM, MUON_POLY, MUON_UPDATE = 0, 1, 2  # ga_muon_gemm's kinds
+MUON_PREP_TILE = 64  # edge of a prepare / apply job tile
+
+
+def muon_fields():
+    """int64 fields of a row of the Muon matrix table (ga_muon_fields)."""
+    return int(lib().ga_muon_fields())
+
+
+def _muon_tables(who, jobs, mats, *others):
+    _gpu(jobs, mats, *others)
+    if jobs.dtype != torch.int32 or jobs.dim() != 2 or jobs.shape[1] != 4 or not jobs.is_contiguous():
+        raise ValueError(f"{who}: jobs must be a contiguous int32 [njobs, 4] table")
+    if mats.dtype != torch.int64 or mats.dim() != 2 or mats.shape[1] != muon_fields() or not mats.is_contiguous():
+        raise ValueError(f"{who}: mats must be a contiguous int64 [nmats, {muon_fields()}] table")
+    return jobs.shape[0]
+
+
+def _muon_row(who, t):
+    if t.dtype != torch.float32 or t.dim() != 1 or t.stride(0) != 1:
+        raise ValueError(f"{who}: one fp32 replica row")
+
+
+def _muon_ws(who, ws):
+    if ws.dtype != torch.bfloat16 or not ws.is_contiguous():
+        raise ValueError(f"{who}: the workspace is a contiguous bfloat16 buffer")
+
+
+def muon_prepare(jobs, mats, grad, buf, workspace, partials, *, momentum, one_m_momentum, nesterov, clip_coef=None):
+    """Momentum, bf16(u) into the workspace in both orientations and the per-job
+    sums of squares for the Muon matrices of one replica row (ga_muon_prepare)."""
+    njobs = _muon_tables("muon_prepare", jobs, mats, grad, buf, workspace, partials, clip_coef)
+    _muon_row("muon_prepare", grad)
+    _muon_row("muon_prepare", buf)
+    _muon_ws("muon_prepare", workspace)
+    if partials.dtype != torch.float32 or partials.numel() < njobs:
+        raise ValueError("muon_prepare: partials must hold one float per job")
+    check(lib().ga_muon_prepare(_p(jobs), njobs, _p(mats), _p(grad), _p(buf), _p(workspace), _p(partials),
+                                float(momentum), float(one_m_momentum), int(bool(nesterov)), _p(clip_coef),
+                                _stream()), "ga_muon_prepare")
+
+
+def muon_scale(mats, partials, eps, scale):
+    """scale[t] = 1 / max(||bf16(u_t)||_F, eps) from prepare's partials (ga_muon_scale)."""
+    _gpu(mats, partials, scale)
+    if mats.dtype != torch.int64 or mats.dim() != 2 or mats.shape[1] != muon_fields() or not mats.is_contiguous():
+        raise ValueError("muon_scale: mats must be a contiguous int64 matrix table")
+    if scale.dtype != torch.float32 or scale.numel() < mats.shape[0] or partials.dtype != torch.float32:
+        raise ValueError("muon_scale: scale must hold one float per matrix")
+    check(lib().ga_muon_scale(_p(mats), mats.shape[0], _p(partials), float(eps), _p(scale), _stream()),
+          "ga_muon_scale")
+
+
+def muon_gemm(kind, tile, jobs, mats, workspace, parity, alpha, beta, scale=None):
+    """One grouped product of a Newton-Schulz iteration over a job table (ga_muon_gemm)."""
+    njobs = _muon_tables("muon_gemm", jobs, mats, workspace, scale)
+    _muon_ws("muon_gemm", workspace)
+    check(lib().ga_muon_gemm(int(kind), int(tile), _p(jobs), njobs, _p(mats), _p(workspace), int(parity),
+                             float(alpha), float(beta), _p(scale), _stream()), "ga_muon_gemm")
+
+
+def muon_apply(jobs, mats, param, workspace, parity, *, lr, wd_factor, scale=None):
+    """p = p wd_factor - lr ratio scale O over the Muon matrices of one replica row (ga_muon_apply)."""
+    njobs = _muon_tables("muon_apply", jobs, mats, param, workspace, scale)
+    _muon_row("muon_apply", param)
+    _muon_ws("muon_apply", workspace)
+    check(lib().ga_muon_apply(_p(jobs), njobs, _p(mats), _p(param), _p(workspace), int(parity), _p(scale),
+                              float(lr), float(wd_factor), _stream()), "ga_muon_apply")
+
+
 _GA_F32 = _lib.GA_F32

@@ -91,6 +91,8 @@ class _PerNodeOptim:
         self.opts = [spec.build(m) for m in models]
         self.arenas = arenas
         self.param_groups = self.opts[0].param_groups
+        if hasattr(self.opts[0], "muon_names"):  # an unfused "muon" spec: Strategy.__config__ reports the selection
+            self.muon_names = self.opts[0].muon_names
 
     def step(self, max_norm=None):
         for a, o in zip(self.arenas, self.opts):
@@ -152,7 +154,7 @@ class ReplicaRunner:
         else:
             spec = s.optim_spec if isinstance(s, SimpleReduceStrategy) else s.inner_optim_spec
             # one fused launch over all K nodes (ArenaAdam / ArenaSGD), or K torch optimizers
-            self.optim = (build_fused(spec, self.ra.params, self.ra, s.placement_opt)
+            self.optim = (build_fused(spec, self.ra.params, self.ra, s.placement_opt, models=models)
                           or _PerNodeOptim(spec, models, self.ra.arenas))
             # a falsy max_norm: no clipping, on the fused and the per-node optimizers alike
             self.max_norm = (s.kwargs.get("max_norm") if isinstance(s, DiLoCoStrategy) else s.max_norm) or None

@@ -44,7 +44,7 @@ def build_inner_optimizer(spec, model, arena, placement=True):
     reference (OptimSpec.build, optim.py:38-39).  GA_FUSED_OPTIM=0 keeps torch's
     optimizer."""
     from ..fused_optim import build_fused
-    return build_fused(spec, model.parameters(), arena, placement) or spec.build(model)
+    return build_fused(spec, model.parameters(), arena, placement, models=[model]) or spec.build(model)
 
 
 def clip_and_step(optim, arena, max_norm):
@@ -167,6 +167,9 @@ class Strategy(ABC, LogModule):
                                   "arena", "coll", "engine", "outer"])
         cfg["strategy"] = self.__class__.__name__
         cfg["placement"] = {"enabled": self.placement_opt is not False, "records": self.placement_records()}
+        muon = getattr(getattr(self, "optim", None), "muon_names", None)
+        if muon is not None:  # a "muon" spec: the matrices it selected (MuonAdamW / ArenaMuon)
+            cfg["muon_matrices"] = list(muon)
         return cfg
 
 

@@ -947,6 +947,85 @@ GA_API int ga_sgd_step(int dtype, void* param, void* grad, float* momentum_buf, 
                        float neg_lr, float momentum, float one_m_dampening, float weight_decay, int nesterov,
                        int first, const float* clip_coef, hipStream_t stream);
 
+/* ---- Muon inner step: batched Newton-Schulz on the bf16 MFMA ------------- */
+
+/*
+ * The Muon step of torch.optim.Muon (torch/optim/_muon.py: _single_tensor_muon,
+ * _zeropower_via_newtonschulz, _adjust_lr) over all the Muon matrices of one replica row
+ * of an fp32 arena, as a handful of launches over job tables instead of ~15 GEMMs and as
+ * many elementwise ops per matrix.  The tables are built once per arena layout on the host
+ * (gym_amd.fused_optim.MuonPlan) and live in device memory:
+ *   mats   int64 [nmats, ga_muon_fields()] rows {off, rows, cols, m_pad, n_pad, x, xt0, xt1, a,
+ *          b, tall, job0, njobs, ratio, 0, 0}: the matrix at arena offset `off` (row-major
+ *          rows x cols), oriented so m = min(rows, cols) <= n (tall = rows > cols: X = u^T),
+ *          m_pad / n_pad = m / n rounded up to whole macro tiles, x / xt0 / xt1 / a / b the
+ *          element offsets in the bf16 workspace of X (m_pad x n_pad), two copies of X^T
+ *          (n_pad x m_pad) and A, B (m_pad x m_pad), [job0, job0 + njobs) its jobs in the
+ *          prepare table, ratio the bits of the float adjusted_lr / lr.
+ *   jobs   int32 [njobs, 4] rows {matrix, tile row, tile column, 0}, one workgroup each.
+ * The workspace starts zeroed.  The products read and write whole tiles, padding included:
+ * zero rows and columns of X give zero rows and columns of A, B and B X, so for finite inputs
+ * the padding is rewritten with exact zeros and no product needs edge code.  (A non-finite
+ * gradient puts NaN into the padding for good; the parameters are NaN then as well, as torch's.)
+ * ga_muon_fields: the number of int64 fields of a `mats` row (16).
+ */
+GA_API int ga_muon_fields(void);
+
+/*
+ * Per element of every 64 x 64 job tile (grad, buf: the replica's rows, fp32):
+ *   g   = grad * clip_coef[0]   (and written back) if clip_coef != null and !(clip_coef[0] >= 1)
+ *   buf = lerp(buf, g, one_m_momentum)                 (torch's lerp; 1 - momentum, computed by the caller in double)
+ *   u   = nesterov ? lerp(g, buf, momentum) : buf
+ * bf16(u) goes to the workspace in both orientations (X and X^T copy 0, one of them through
+ * LDS), and partials[job] = the sum of bf16(u)^2 over the tile in a fixed order (no atomics).
+ * Replaces: `buf.lerp_(grad, 1 - momentum)`, `grad.lerp(buf, momentum)` and `grad.bfloat16()`
+ * (with the `.T` of a tall matrix) per parameter in torch/optim/_muon.py (_single_tensor_muon,
+ * _zeropower_via_newtonschulz), behind the reference's `self.optim.step()`
+ * (exogym/strategy/strategy.py:140, diloco.py:59, communicate_optimize_strategy.py:74).
+ */
+GA_API int ga_muon_prepare(const int32_t* jobs, int64_t njobs, const int64_t* mats, float* grad, float* buf,
+                           void* workspace, float* partials, float momentum, float one_m_momentum, int nesterov,
+                           const float* clip_coef, hipStream_t stream);
+
+/*
+ * scale[t] = 1 / max(sqrt(sum of matrix t's partials, ascending), eps): the normalisation
+ * X / max(||X||_F, eps) of _zeropower_via_newtonschulz, which the first iteration's scalars
+ * carry (A = s^2 U U^T, X' = a s U + s B U) and, with ns_steps = 0, the apply.
+ * Replaces: `ortho_grad.div_(ortho_grad.norm().clamp(min=eps))` per parameter
+ * (torch/optim/_muon.py, _zeropower_via_newtonschulz), behind the same `self.optim.step()`.
+ */
+GA_API int ga_muon_scale(const int64_t* mats, int64_t nmats, const float* partials, float eps, float* scale,
+                         hipStream_t stream);
+
+/*
+ * One grouped product C = alpha * D + beta * (L R^T) over all matrices of a job table: bf16
+ * operands, fp32 accumulation on v_mfma_f32_32x32x16_bf16, bf16 stored once.  tile = 128 or
+ * 64: the macro tile of the table's matrices (256 threads, four waves of (tile/2)^2).
+ *   kind 0 (gram)    A = X X^T               jobs: tile column >= tile row, the mirror stored too
+ *   kind 1 (poly)    B = alpha A + beta A A^T  (same jobs)
+ *   kind 2 (update)  X = alpha X + beta B X, written to X in place and transposed to X^T copy
+ *                    parity ^ 1 (R = X^T copy `parity`)
+ * scale != null (the first iteration): beta *= scale[t]^2 for kind 0, alpha and beta *=
+ * scale[t] for kind 2.
+ * Replaces: per parameter and iteration `ortho_grad @ ortho_grad.T` and the two `torch.addmm`
+ * calls of _zeropower_via_newtonschulz (torch/optim/_muon.py), behind the same `self.optim.step()`.
+ */
+GA_API int ga_muon_gemm(int kind, int tile, const int32_t* jobs, int64_t njobs, const int64_t* mats,
+                        void* workspace, int parity, float alpha, float beta, const float* scale,
+                        hipStream_t stream);
+
+/*
+ * p = p * wd_factor - (lr * ratio) * scale[t] * O over the prepare job tiles, O = the final X
+ * oriented back (X, or X^T copy `parity` of a tall matrix); scale null: 1.  wd_factor = 1 -
+ * lr * weight_decay, computed by the caller in double.  Only elements of the jobs' matrices
+ * are written.
+ * Replaces: `self.optim.step()` of an inner torch.optim.Muon (the reference's OptimSpec
+ * builds any torch optimizer by class, exogym/strategy/optim.py:38-39).
+ */
+GA_API int ga_muon_apply(const int32_t* jobs, int64_t njobs, const int64_t* mats, float* param,
+                         const void* workspace, int parity, const float* scale, float lr, float wd_factor,
+                         hipStream_t stream);
+
 /* ---- node drift: model correlation and consensus distance ---------------- */
 
 /* Bytes of the `work` buffer ga_replica_gram needs for K replicas of n elements
