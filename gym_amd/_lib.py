@@ -134,6 +134,13 @@ SIGNATURES = {
     "ga_muon_scale": (c_i32, [c_p, c_i64, c_p, c_f32, c_p, c_p]),
     "ga_muon_gemm": (c_i32, [c_i32, c_i32, c_p, c_i64, c_p, c_p, c_i32, c_f32, c_f32, c_p, c_p]),
     "ga_muon_apply": (c_i32, [c_p, c_i64, c_p, c_p, c_p, c_i32, c_p, c_f32, c_f32, c_p]),
+    "ga_adafactor_fields": (c_i32, []),
+    "ga_adafactor_stats": (c_i32, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_f32, c_p, c_p]),
+    "ga_adafactor_reduce": (c_i32, [c_p, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_f32, c_f32, c_f32, c_f32, c_p]),
+    "ga_adafactor_unorm": (c_i32, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_f32, c_p]),
+    "ga_adafactor_scale": (c_i32, [c_p, c_i64, c_p, c_i64, c_i64, c_f32, c_p]),
+    "ga_adafactor_apply": (c_i32, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_f32, c_f32,
+                                   c_p]),
     "ga_replica_gram_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "ga_replica_gram_chain": (c_i32, []),
     "ga_replica_gram": (c_i32, [c_i32, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p]),

@@ -34,8 +34,12 @@ write p, buf) with momentum, dampening, Nesterov and L2 weight decay, a
 per-parameter initialised flag where Adam has a step count.  ArenaMuon is the
 "muon" spec (strategy.optim.MuonAdamW): Muon's Newton-Schulz iterations on the
 hidden matrices as grouped bf16 MFMA launches over job tables (ga_muon_*), an
-inner ArenaAdam on the rest.  build_fused picks the class for a spec; FUSED
-names them for the callers that step them.
+inner ArenaAdam on the rest.  ArenaAdafactor is torch.optim.Adafactor (the
+"adafactor" spec) on arenas of tensors with at most two dimensions: five launches
+over job tables (ga_adafactor_*) that cover all K replicas, and a state of one
+row vector and one column vector per matrix instead of full-size moments.
+build_fused picks the class for a spec; FUSED names them for the callers that
+step them.
 """
 import math
 import time
@@ -43,6 +47,7 @@ import time
 import torch
 
 from . import ops
+from .ops import ADAFACTOR_CHUNK, ADAFACTOR_FIELDS, ADAFACTOR_TILE  # geometry of csrc/adafactor.hip
 
 _UNSUPPORTED = ("amsgrad", "maximize", "capturable", "differentiable")
 
@@ -870,12 +875,268 @@ def fusable_muon(spec_cls, kwargs, arena):
     return not any(isinstance(kw.get(k), torch.Tensor) for k in ("lr", "adamw_lr"))
 
 
-FUSED = (ArenaAdam, ArenaSGD, ArenaMuon)  # the inner optimizers whose step(max_norm=) clips on the device
+_ADAFACTOR_KW = ("lr", "beta2_decay", "eps", "d", "weight_decay")
+# torch.optim.Adafactor specs run as ArenaAdafactor: faster than torch's step in every alternated
+# pair at K = 1 and K = 8 (profiles/inner_adafactor.txt); False keeps them on torch
+ADAFACTOR_FUSED_DEFAULT = True
+ADAFACTOR_PLAN_CACHE = 8  # present sets whose device tables an ArenaAdafactor keeps (least recently used evicted)
+
+
+def fusable_adafactor(spec_cls, kwargs, arena):
+    """True when OptimSpec(spec_cls, **kwargs) can run as ArenaAdafactor on this arena:
+    torch.optim.Adafactor on an fp32 arena with a gradient set, no maximize, a float
+    learning rate, and no tensor of more than two dimensions (torch factors the last
+    two dimensions of an N-D tensor batch-wise; that is not built)."""
+    if spec_cls is not getattr(torch.optim, "Adafactor", None) or not _fp32_arena(arena):
+        return False
+    kw = dict(kwargs or {})
+    if kw.get("maximize") or set(kw) - (set(_ADAFACTOR_KW) | {"foreach", "maximize"}):
+        return False
+    if isinstance(kw.get("lr", 1e-2), torch.Tensor):
+        return False
+    return all(len(s) <= 2 for s in arena.layout.shapes)
+
+
+def adafactor_slots(shapes, offsets):
+    """What is fixed for an arena layout whichever tensors are present.  Per tensor
+    (None for an empty one) the dict of its tensor-table fields but the job range: a
+    2-D tensor is a matrix of rt x ct tiles whose state is row_var [rows] then col_var
+    [cols]; any other a vector of rt chunks whose state is its variance.  Returns
+    (slots, state row length, work row length, jobs of all tensors): the work row
+    holds every tensor's partials and scalars and, behind them, psq and usq for
+    that many jobs."""
+    TR, TC = ADAFACTOR_TILE
+    slots, st, wk, jobs = [], 0, 0, 0
+    for shape, off in zip(shapes, offsets):
+        n = math.prod(shape)
+        if n == 0:
+            slots.append(None)
+            continue
+        if len(shape) == 2:
+            rows, cols = shape
+            s = dict(off=off, rows=rows, cols=cols, matrix=1, state=st, rt=-(-rows // TR), ct=-(-cols // TC))
+            st += _round_up(rows + cols, 4)
+        else:
+            s = dict(off=off, rows=1, cols=n, matrix=0, state=st, rt=-(-n // ADAFACTOR_CHUNK), ct=1)
+            st += _round_up(n, 4)
+        s["rowpart"], s["colpart"] = wk, wk + s["ct"] * s["rows"] * s["matrix"]
+        s["scal"] = s["colpart"] + s["rt"] * s["cols"] * s["matrix"]
+        wk = s["scal"] + 4
+        jobs += s["rt"] * s["ct"]
+        slots.append(s)
+    return slots, max(st, 4), wk + 2 * jobs, jobs
+
+
+def adafactor_tables(slots, present, psq0):
+    """The tensor table and the job table (lists of rows, include/gym_amd.h
+    "Adafactor inner step") of the tensors `present` (indices into slots); psq0: the
+    work offset of psq, usq follows it for as many jobs as all slots have."""
+    total = sum(s["rt"] * s["ct"] for s in slots if s is not None)
+    tens, jobs = [], []
+    for t, s in enumerate(slots[i] for i in present):
+        job0 = len(jobs)
+        jobs += [(t, i, j, 0) for i in range(s["rt"]) for j in range(s["ct"])]
+        row = [s["off"], s["rows"], s["cols"], s["matrix"], s["state"], s["rowpart"], s["colpart"], job0,
+               len(jobs) - job0, s["rt"], s["ct"], psq0 + job0, psq0 + total + job0, s["scal"]]
+        tens.append(row + [0] * (ADAFACTOR_FIELDS - len(row)))
+    return tens, jobs
+
+
+class AdafactorPlan:
+    """The device tables of one Adafactor pass over the tensors `present`."""
+
+    def __init__(self, slots, present, psq0, device):
+        tens, jobs = adafactor_tables(slots, present, psq0)
+        self.tens = torch.tensor(tens, dtype=torch.int64).reshape(-1, ADAFACTOR_FIELDS).to(device)
+        self.jobs = torch.tensor(jobs, dtype=torch.int32).reshape(-1, 4).to(device)
+
+
+class ArenaAdafactor(_ArenaOptimizer):
+    """torch.optim.Adafactor (torch/optim/_adafactor.py, _single_tensor_adafactor) over
+    one node's ParamArena or a ReplicaArena whose tensors have at most two dimensions:
+    step() is five launches over job tables that cover all K replicas
+    (ga_adafactor_stats, reduce, unorm, scale, apply) and, with clipping, one
+    ga_grad_clip_coef whose coefficient the first of them applies on the device.  No
+    host synchronisation, where torch's step reads two norms back per tensor.
+
+    The state is one fp32 [K, ls] set of row_var + col_var floats per matrix and numel
+    per vector, and there is no first moment; state[p] holds `step`, and `row_var`
+    [R, 1] and `col_var` [1, C] (or `variance`) as views of it, so state_dict() has
+    torch's layout and load_state_dict() takes an ArenaAdafactor or a
+    torch.optim.Adafactor state dict.  A parameter whose .grad is None is skipped as
+    torch skips it (no decay, no state update, its own `step` does not advance): the
+    tables are built for the present set and cached by it, and tensors on different
+    counts (beta2t and rho are scalars of a launch) take their passes in turn.  While
+    every parameter has had a gradient on every step they share one count tensor."""
+
+    def __init__(self, params, arena, lr=1e-2, beta2_decay=-0.8, eps=(None, 1e-3), d=1.0, weight_decay=0.0,
+                 foreach=None, maximize=False, placement=True):
+        if isinstance(lr, torch.Tensor) or maximize:
+            raise ValueError("ArenaAdafactor: a float lr and no maximize (fusable_adafactor)")
+        if not 0.0 <= lr:
+            raise ValueError(f"Learning rate should be >= 0 but is: {lr}")
+        if not 0.0 >= beta2_decay:
+            raise ValueError(f"beta2_decay should be <= 0 but is: {beta2_decay}")
+        if eps[0] is not None and not 0.0 <= eps[0]:
+            raise ValueError(f"epsilon1 should be >= 0 but is: {eps[0]}")
+        if not 0.0 <= eps[1]:
+            raise ValueError(f"epsilon2 should be >= 0 but is: {eps[1]}")
+        if not 1.0 <= d:
+            raise ValueError(f"Clipping threshold d should be >= 1 but is: {d}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"weight_decay should be >= 0 but is: {weight_decay}")
+        defaults = dict(lr=lr, beta2_decay=beta2_decay, eps=tuple(eps), d=d, weight_decay=weight_decay,
+                        foreach=None, maximize=False)  # foreach: accepted and ignored
+        super().__init__(params, defaults, arena)
+        layout = self.arenas[0].layout
+        shape_at = dict(zip(layout.offsets, layout.shapes))
+        owned = [(o, n) for _, o, n in self._spans[0]]
+        if any([(o, n) for _, o, n in sp] != owned for sp in self._spans):
+            raise ValueError("ArenaAdafactor: every replica must own the same tensors")
+        shapes = [shape_at[o] for o, _ in owned]
+        if any(len(s) > 2 for s in shapes):
+            raise ValueError("ArenaAdafactor: tensors of more than two dimensions are not built (fusable_adafactor)")
+        self._slots, self.ls, self.lw, njobs = adafactor_slots(shapes, [o for o, _ in owned])
+        self._psq0 = self.lw - 2 * njobs
+        dev = self.P.device
+        self._S = torch.zeros(self.K, self.ls, dtype=torch.float32, device=dev)  # the state set
+        self._W = torch.zeros(self.K, self.lw, dtype=torch.float32, device=dev)  # partials and scalars
+        self._slot_of = {id(p): (k, i) for k, sp in enumerate(self._spans) for i, (p, _, _) in enumerate(sp)}
+        self._count = [[0.0] * len(owned) for _ in range(self.K)]  # the step count of every tensor
+        self._clock = torch.tensor(0.0)  # the one count tensor while all tensors share a count, else None
+        self._plans = {}
+        for p in self.param_groups[0]["params"]:
+            self._bind_state(p, self._clock)
+        self.placement = {"placed": False, "why": "no search for Adafactor"}
+
+    @property
+    def S(self):
+        """The state set [K, ls]: per matrix row_var then col_var, per vector its variance."""
+        return self._S
+
+    def state_bytes(self):
+        return self._S.numel() * 4
+
+    def _bind_state(self, p, step):
+        k, i = self._slot_of[id(p)]
+        s = self._slots[i]
+        if s is None:
+            self.state[p] = {"step": step}
+        elif s["matrix"]:
+            a, R, C = s["state"], s["rows"], s["cols"]
+            self.state[p] = {"step": step, "row_var": self._S[k, a:a + R].view(R, 1),
+                             "col_var": self._S[k, a + R:a + R + C].view(1, C)}
+        else:
+            a = s["state"]
+            self.state[p] = {"step": step, "variance": self._S[k, a:a + s["cols"]].view(p.shape)}
+
+    def state_dict(self):
+        """torch's layout, every parameter with a `step` tensor of its own."""
+        sd = super().state_dict()
+        sd["state"] = {i: {**st, "step": st["step"].clone()} for i, st in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """torch's Optimizer.load_state_dict, then the loaded factors are copied into
+        the flat state set and the state is re-pointed at its views.  A parameter
+        without an entry starts at step 0 with zero state."""
+        super().load_state_dict(state_dict)
+        loaded = {id(p): dict(self.state.get(p, {})) for p in self.param_groups[0]["params"]}
+        counts = {i: float(st.get("step", 0.0)) for i, st in loaded.items()}
+        self._clock = torch.tensor(next(iter(counts.values()))) if len(set(counts.values())) == 1 else None
+        with torch.no_grad():
+            self._S.zero_()
+            for p in self.param_groups[0]["params"]:
+                k, i = self._slot_of[id(p)]
+                self._count[k][i] = counts[id(p)]
+                self._bind_state(p, self._clock if self._clock is not None else torch.tensor(counts[id(p)]))
+                for key in ("row_var", "col_var", "variance"):
+                    if key in loaded[id(p)] and key in self.state[p]:
+                        self.state[p][key].copy_(loaded[id(p)][key].reshape(self.state[p][key].shape))
+
+    def _plan(self, present):
+        plan = self._plans.pop(present, None)
+        if plan is None:
+            plan = AdafactorPlan(self._slots, present, self._psq0, self.P.device)
+            while len(self._plans) >= ADAFACTOR_PLAN_CACHE:  # the least recently used set goes
+                del self._plans[next(iter(self._plans))]
+        self._plans[present] = plan  # most recently used last
+        return plan
+
+    def _advance(self, present):
+        """Advance the count of every present tensor; returns per replica {count: the
+        present tensors on it}."""
+        everything = all(len(pr) == sum(s is not None for s in self._slots) for pr in present)
+        if self._clock is not None and everything:
+            self._clock += 1  # every tensor present on one count: nothing per parameter
+            t = float(self._clock)
+            self._count = [[t] * len(c) for c in self._count]
+            return [{t: pr} for pr in present]
+        if self._clock is not None:  # from here on every parameter counts for itself
+            for p in self.param_groups[0]["params"]:
+                self.state[p]["step"] = self._clock.clone()
+            self._clock = None
+        groups = []
+        for k, pr in enumerate(present):
+            by_count = {}
+            for i in pr:
+                self.state[self._spans[k][i][0]]["step"] += 1
+                self._count[k][i] += 1.0
+                by_count.setdefault(self._count[k][i], []).append(i)
+            groups.append({t: tuple(idx) for t, idx in by_count.items()})
+        return groups
+
+    def _pass(self, k, t, present, clip):
+        """The five launches for the tensors `present`, all on count t, of replica k (None: of every replica)."""
+        g = self.param_groups[0]
+        lr, wd, (eps1, eps2) = float(g["lr"]), float(g["weight_decay"]), g["eps"]
+        eps1 = torch.finfo(torch.float32).eps if eps1 is None else float(eps1)
+        beta2t, rho = t ** float(g["beta2_decay"]), min(lr, 1 / math.sqrt(t))
+        plan = self._plan(present)
+        P, G, S, W = ((x if k is None else x[k:k + 1]) for x in (self.P, self.G, self._S, self._W))
+        if clip is not None and k is not None:
+            clip = clip[2 * k:2 * k + 2]
+        ops.adafactor_stats(plan.jobs, plan.tens, P, G, S, W, beta2t=beta2t, clip_coef=clip)
+        ops.adafactor_reduce(plan.tens, S, W, beta2t=beta2t, rho=rho, eps1=eps1, eps2=float(eps2))
+        ops.adafactor_unorm(plan.jobs, plan.tens, G, S, W, eps1=eps1)
+        ops.adafactor_scale(plan.tens, W, d=float(g["d"]))
+        ops.adafactor_apply(plan.jobs, plan.tens, P, G, S, W, eps1=eps1,
+                            wd_factor=(1 - lr * wd) if wd != 0 else 1.0)
+
+    @torch.no_grad()
+    def step(self, closure=None, max_norm=None, clip=None):
+        """clip: the coefficients of a ga_grad_clip_coef the caller already ran over the gradient set."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for ar in self.arenas:
+            ar.sync_grads()
+        present = [tuple(i for i, (p, _, _) in enumerate(sp) if p.grad is not None and self._slots[i] is not None)
+                   for sp in self._spans]
+        if not any(present):  # no parameter has a gradient: torch's step does nothing
+            return loss
+        groups = self._advance(present)
+        if clip is None and max_norm:
+            ops.grad_clip_coef(self.G, self.ld, max_norm, self._partials, self._clip)
+            clip = self._clip
+        if all(g == groups[0] for g in groups):  # one launch set covers the K rows
+            for t, idx in groups[0].items():
+                self._pass(None, t, idx, clip)
+        else:
+            for k, by_count in enumerate(groups):
+                for t, idx in by_count.items():
+                    self._pass(k, t, idx, clip)
+        return loss
+
+
+FUSED = (ArenaAdam, ArenaSGD, ArenaMuon, ArenaAdafactor)  # the inner optimizers whose step(max_norm=) clips on the device
 
 
 def build_fused(spec, params, arena, placement=True, models=None):
     """The fused inner optimizer of OptimSpec `spec` over `arena` (ArenaAdam for
-    torch's AdamW / Adam, ArenaSGD for torch's SGD, ArenaMuon for MuonAdamW with
+    torch's AdamW / Adam, ArenaSGD for torch's SGD, ArenaAdafactor for torch's
+    Adafactor under ADAFACTOR_FUSED_DEFAULT, ArenaMuon for MuonAdamW with
     `fused=True` -- MUON_FUSED_DEFAULT without the kwarg), or None when the spec
     stays on torch: another optimizer or option, a bf16 arena, or
     GA_FUSED_OPTIM=0.  models: the arena's modules (one per replica), from which
@@ -908,4 +1169,8 @@ def build_fused(spec, params, arena, placement=True, models=None):
     # a stand-in kernel layer (tests) written before ga_sgd_step keeps torch's SGD; gym_amd.ops always has it
     if fusable_sgd(spec.cls, kw, arena) and hasattr(ops, "sgd_step"):
         return ArenaSGD(params, arena, placement=placement, **{k: v for k, v in kw.items() if k in _SGD_KW})
+    # likewise a stand-in layer written before ga_adafactor_* keeps torch's Adafactor
+    if ADAFACTOR_FUSED_DEFAULT and fusable_adafactor(spec.cls, kw, arena) and hasattr(ops, "adafactor_stats"):
+        return ArenaAdafactor(params, arena, placement=placement,
+                              **{k: v for k, v in kw.items() if k in _ADAFACTOR_KW})
     return None

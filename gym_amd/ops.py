@@ -1155,4 +1155,67 @@ def muon_apply(jobs, mats, param, workspace, parity, *, lr, wd_factor, scale=Non
                               float(lr), float(wd_factor), _stream()), "ga_muon_apply")
 
 
+ADAFACTOR_TILE = (64, 256)  # rows x columns of a matrix job tile
+ADAFACTOR_CHUNK = 4096  # elements of a vector job
+ADAFACTOR_FIELDS = 16  # int64 fields of a tensor table row (ga_adafactor_fields)
+
+
+def _adafactor_args(who, jobs, tens, sets, clip_coef=None):
+    """(njobs | None, ntens, K, row lengths of `sets`): the tables and the fp32 [K, l]
+    sets (param / grad, state, work) of one ga_adafactor_* call, checked."""
+    _gpu(jobs, tens, *sets, clip_coef)
+    if jobs is not None and (jobs.dtype != torch.int32 or jobs.dim() != 2 or jobs.shape[1] != 4
+                             or not jobs.is_contiguous()):
+        raise ValueError(f"{who}: jobs must be a contiguous int32 [njobs, 4] table")
+    if tens.dtype != torch.int64 or tens.dim() != 2 or tens.shape[1] != ADAFACTOR_FIELDS or not tens.is_contiguous():
+        raise ValueError(f"{who}: tens must be a contiguous int64 [ntens, {ADAFACTOR_FIELDS}] table")
+    K, lds = sets[0].shape[0], []
+    for t in sets:
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != K or t.stride(1) != 1:
+            raise ValueError(f"{who}: fp32 [K, l] sets of one K")
+        lds.append(_rows_ld(t)[1])
+    if clip_coef is not None and clip_coef.numel() < 2 * K:
+        raise ValueError(f"{who}: clip_coef must hold 2 floats per replica")
+    return (jobs.shape[0] if jobs is not None else None), tens.shape[0], K, lds
+
+
+def adafactor_stats(jobs, tens, param, grad, state, work, *, beta2t, clip_coef=None):
+    """Row / column sums of g^2 and sums of p^2 per job, the vectors' variance in
+    place, the clipped gradient written back (ga_adafactor_stats)."""
+    nj, _, K, (ld, ld_g, ls, lw) = _adafactor_args("adafactor_stats", jobs, tens, (param, grad, state, work), clip_coef)
+    if ld != ld_g:
+        raise ValueError("adafactor_stats: param and grad must share one layout")
+    check(lib().ga_adafactor_stats(_p(jobs), nj, _p(tens), _p(param), _p(grad), _p(state), _p(work), K, ld, ls, lw,
+                                   float(beta2t), _p(clip_coef), _stream()), "ga_adafactor_stats")
+
+
+def adafactor_reduce(tens, state, work, *, beta2t, rho, eps1, eps2):
+    """row_var / col_var, their clamped mean and alpha per tensor (ga_adafactor_reduce)."""
+    _, nt, K, (ls, lw) = _adafactor_args("adafactor_reduce", None, tens, (state, work))
+    check(lib().ga_adafactor_reduce(_p(tens), nt, _p(state), _p(work), K, ls, lw, float(beta2t), float(rho),
+                                    float(eps1), float(eps2), _stream()), "ga_adafactor_reduce")
+
+
+def adafactor_unorm(jobs, tens, grad, state, work, *, eps1):
+    """The jobs' sums of u^2 (ga_adafactor_unorm)."""
+    nj, _, K, (ld, ls, lw) = _adafactor_args("adafactor_unorm", jobs, tens, (grad, state, work))
+    check(lib().ga_adafactor_unorm(_p(jobs), nj, _p(tens), _p(grad), _p(state), _p(work), K, ld, ls, lw, float(eps1),
+                                   _stream()), "ga_adafactor_unorm")
+
+
+def adafactor_scale(tens, work, *, d):
+    """step = -alpha / max(1, RMS(u) / d) per tensor (ga_adafactor_scale)."""
+    _, nt, K, (lw,) = _adafactor_args("adafactor_scale", None, tens, (work,))
+    check(lib().ga_adafactor_scale(_p(tens), nt, _p(work), K, lw, float(d), _stream()), "ga_adafactor_scale")
+
+
+def adafactor_apply(jobs, tens, param, grad, state, work, *, eps1, wd_factor):
+    """p = p wd_factor + step u over the jobs (ga_adafactor_apply)."""
+    nj, _, K, (ld, ld_g, ls, lw) = _adafactor_args("adafactor_apply", jobs, tens, (param, grad, state, work))
+    if ld != ld_g:
+        raise ValueError("adafactor_apply: param and grad must share one layout")
+    check(lib().ga_adafactor_apply(_p(jobs), nj, _p(tens), _p(param), _p(grad), _p(state), _p(work), K, ld, ls, lw,
+                                   float(eps1), float(wd_factor), _stream()), "ga_adafactor_apply")
+
+
 _GA_F32 = _lib.GA_F32

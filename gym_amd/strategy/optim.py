@@ -120,6 +120,7 @@ _BY_NAME = {
     "sgd": torch.optim.SGD,
     "rmsprop": torch.optim.RMSprop,
     "adagrad": torch.optim.Adagrad,
+    "adafactor": torch.optim.Adafactor,  # beyond the reference; fused: gym_amd.fused_optim.ArenaAdafactor
     "muon": MuonAdamW,
 }
 

@@ -1026,6 +1026,90 @@ GA_API int ga_muon_apply(const int32_t* jobs, int64_t njobs, const int64_t* mats
                          const void* workspace, int parity, const float* scale, float lr, float wd_factor,
                          hipStream_t stream);
 
+/* ---- Adafactor inner step: factored second moments over job tables -------- */
+
+/*
+ * The Adafactor step of torch.optim.Adafactor (torch/optim/_adafactor.py,
+ * _single_tensor_adafactor) over tensors of K replica rows of an fp32 arena (param, grad:
+ * [K, ld] sets), as five launches over job tables instead of two norms, a full-size rank-1
+ * product and two host synchronisations per tensor.  The tables are built once per arena
+ * layout and present set on the host (gym_amd.fused_optim.AdafactorPlan) and live in device
+ * memory:
+ *   tens   int64 [ntens, ga_adafactor_fields()] rows {off, rows, cols, matrix, state, rowpart,
+ *          colpart, job0, njobs, rt, ct, psq, usq, scal, 0, 0}: the tensor at arena offset `off`,
+ *          a row-major rows x cols matrix (matrix = 1; rt x ct tiles of 64 x 256) or a vector of
+ *          rows * cols elements (matrix = 0; rt chunks of 4096), [job0, job0 + njobs) its jobs.
+ *          `state` is an offset into a row of the state set [K, ls]: row_var [rows] then col_var
+ *          [cols] of a matrix, the variance of a vector.  The others are offsets into a row of
+ *          the work set [K, lw]: rowpart [ct, rows] and colpart [rt, cols] the tiles' row and
+ *          column sums of g^2, psq and usq [njobs] the jobs' sums of p^2 and u^2, scal 4 floats
+ *          {alpha, max(mean(row_var), eps1), step, 0}.
+ *   jobs   int32 [njobs, 4] rows {tensor, tile row | chunk, tile column, 0}, one workgroup each;
+ *          the replica is the second grid dimension.
+ * Every sum has a fixed order and there are no atomics: a step is bit-reproducible.  Only
+ * elements of listed tensors are written.
+ * ga_adafactor_fields: the number of int64 fields of a `tens` row (16).
+ */
+GA_API int ga_adafactor_fields(void);
+
+/*
+ * Per job: g = grad * clip_coef[2k] (and written back) if clip_coef != null and
+ * !(clip_coef[2k] >= 1) (ga_sgd_step's rule).  A matrix tile writes its row sums of g^2 to
+ * rowpart[tile column, row], its column sums to colpart[tile row, column] and its sum of p^2
+ * to psq[job]; a vector chunk updates variance = lerp(variance, g*g, beta2t) (torch's lerp)
+ * in place and writes psq[job].  beta2t = step ** beta2_decay, computed by the caller in double.
+ * Replaces: `torch.norm(grad, dim=-1)`, `torch.norm(grad, dim=-2)`, `param.norm(2).item()` and
+ * `variance.lerp_(grad * grad, ...)` per parameter in torch/optim/_adafactor.py
+ * (_single_tensor_adafactor), and clip_grad_norm_'s scaling, behind the reference's
+ * `self.optim.step()` (exogym/strategy/strategy.py:135-140, diloco.py:52-59,
+ * communicate_optimize_strategy.py:69-74; OptimSpec builds any torch optimizer by class,
+ * exogym/strategy/optim.py:38-39).
+ */
+GA_API int ga_adafactor_stats(const int32_t* jobs, int64_t njobs, const int64_t* tens, const float* param,
+                              float* grad, float* state, float* work, int64_t K, int64_t ld, int64_t ls,
+                              int64_t lw, float beta2t, const float* clip_coef, hipStream_t stream);
+
+/*
+ * Per tensor: the partials added in ascending tile order, row_var = lerp(row_var, sum / cols,
+ * beta2t), col_var = lerp(col_var, sum / rows, beta2t); scal[1] = max(mean(row_var), eps1) of
+ * the updated row_var; scal[0] = alpha = max(eps2, ||p|| / sqrt(numel)) * rho, rho = min(lr,
+ * 1 / sqrt(step)) computed by the caller in double.
+ * Replaces: `row_var.lerp_`, `col_var.lerp_`, `row_var.mean(dim=-2).clamp_(min=eps1)` and the
+ * host arithmetic of `alpha` per parameter (torch/optim/_adafactor.py), behind the same
+ * `self.optim.step()`.
+ */
+GA_API int ga_adafactor_reduce(const int64_t* tens, int64_t ntens, float* state, float* work, int64_t K, int64_t ls,
+                               int64_t lw, float beta2t, float rho, float eps1, float eps2, hipStream_t stream);
+
+/*
+ * Per job: u = rsqrt(max((row_var_i * col_var_j) / scal[1], eps1^2)) * g (a vector: its
+ * variance in place of the quotient), usq[job] = the job's sum of u^2.  Nothing else is written.
+ * Replaces: `row_var @ col_var`, `.div_`, `.clamp_(min=eps1 * eps1).rsqrt_()`, `.mul_(grad)` and
+ * `update.norm(2).item()` per parameter (torch/optim/_adafactor.py), behind the same
+ * `self.optim.step()`.
+ */
+GA_API int ga_adafactor_unorm(const int32_t* jobs, int64_t njobs, const int64_t* tens, const float* grad,
+                              const float* state, float* work, int64_t K, int64_t ld, int64_t ls, int64_t lw,
+                              float eps1, hipStream_t stream);
+
+/*
+ * Per tensor: scal[2] = step = -alpha / max(1, sqrt(sum of usq, fixed order) / (sqrt(numel) * d)).
+ * Replaces: `denom = max(1.0, update.norm(2).item() / ((update.numel() ** 0.5) * d))` per
+ * parameter (torch/optim/_adafactor.py), behind the same `self.optim.step()`.
+ */
+GA_API int ga_adafactor_scale(const int64_t* tens, int64_t ntens, float* work, int64_t K, int64_t lw, float d,
+                              hipStream_t stream);
+
+/*
+ * Per job: u as in ga_adafactor_unorm, p = p * wd_factor + step * u.  wd_factor = 1 - lr *
+ * weight_decay (1 without decay), computed by the caller in double.
+ * Replaces: `param.mul_(1 - lr * weight_decay)` and `param.add_(update, alpha=-alpha / denom)`
+ * per parameter (torch/optim/_adafactor.py), behind the same `self.optim.step()`.
+ */
+GA_API int ga_adafactor_apply(const int32_t* jobs, int64_t njobs, const int64_t* tens, float* param,
+                              const float* grad, const float* state, const float* work, int64_t K, int64_t ld,
+                              int64_t ls, int64_t lw, float eps1, float wd_factor, hipStream_t stream);
+
 /* ---- node drift: model correlation and consensus distance ---------------- */
 
 /* Bytes of the `work` buffer ga_replica_gram needs for K replicas of n elements
