@@ -129,6 +129,9 @@ SIGNATURES = {
                              c_f32, c_f32, c_f32, c_p, c_p]),
     "ga_sgd_step": (c_i32, [c_i32, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32,
                             c_p, c_p]),
+    "ga_adam8_step": (c_i32, [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_f32, c_f32, c_f32,
+                              c_f32, c_f32, c_f32, c_f32, c_f32, c_p, c_p]),
+    "ga_adam8_encode": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i32, c_p, c_p]),
     "ga_muon_fields": (c_i32, []),
     "ga_muon_prepare": (c_i32, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_f32, c_f32, c_i32, c_p, c_p]),
     "ga_muon_scale": (c_i32, [c_p, c_i64, c_p, c_f32, c_p, c_p]),

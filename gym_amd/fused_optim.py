@@ -38,6 +38,8 @@ inner ArenaAdam on the rest.  ArenaAdafactor is torch.optim.Adafactor (the
 "adafactor" spec) on arenas of tensors with at most two dimensions: five launches
 over job tables (ga_adafactor_*) that cover all K replicas, and a state of one
 row vector and one column vector per matrix instead of full-size moments.
+ArenaAdam8bit is the "adamw8bit" spec (strategy.optim.AdamW8bit): AdamW whose two
+moments are 8-bit codes under a scale per 64 elements, one ga_adam8_step launch.
 build_fused picks the class for a spec; FUSED names them for the callers that
 step them.
 """
@@ -48,6 +50,7 @@ import torch
 
 from . import ops
 from .ops import ADAFACTOR_CHUNK, ADAFACTOR_FIELDS, ADAFACTOR_TILE  # geometry of csrc/adafactor.hip
+from .strategy.optim import ADAM8_BLOCK, AdamW8bit, adam_scalars
 
 _UNSUPPORTED = ("amsgrad", "maximize", "capturable", "differentiable")
 
@@ -241,7 +244,81 @@ class _ArenaOptimizer(torch.optim.Optimizer):
         return loss
 
 
-class ArenaAdam(_ArenaOptimizer):
+class _AdamCounts:
+    """What ArenaAdam and ArenaAdam8bit share beside _ArenaOptimizer: a step count per
+    parameter kept as groups of parameters that share one count tensor, the launch
+    ranges of the present parameters by count, and the launch scalars.  The class
+    supplies _bind_state(p): state[p] with its `step` kept and its moments re-pointed."""
+
+    def _start_counts(self):
+        # the step counts: [count tensor, [(param, replica, offset, numel)]] per group of parameters that
+        # share a count -- state[p]["step"] of its members IS the group's tensor, so a step advances a
+        # group with one add.  One group while every parameter has had a gradient on every step.
+        self._groups = [[torch.tensor(0.0), []]]
+        for p in self.param_groups[0]["params"]:
+            self._groups[0][1].append((p, *self._where[id(p)]))
+            self._bind_state(p)
+
+    def state_dict(self):
+        """torch's layout, every parameter with a `step` tensor of its own (here
+        the parameters of a group share one; torch's optimizers, which advance
+        each entry in place, must not)."""
+        sd = super().state_dict()
+        sd["state"] = {i: {**st, "step": st["step"].clone()} for i, st in sd["state"].items()}
+        return sd
+
+    def _regroup(self, steps):
+        """steps: id(param) -> its loaded count.  One group, and one count tensor, per distinct count."""
+        groups = {}
+        for k, sp in enumerate(self._spans):
+            for p, o, n in sp:
+                t = steps[id(p)]
+                g = groups.get(t) or groups.setdefault(t, [torch.tensor(t), []])
+                g[1].append((p, k, o, n))
+                self.state[p]["step"] = g[0]
+                self._bind_state(p)
+        self._groups = list(groups.values())
+
+    def _ranges(self):
+        """Advance the count of every parameter that has a gradient now and
+        return, per replica, [(a, b, t)]: the contiguous ranges of present
+        parameters that share the count t (_join).  A group whose members
+        are all present advances with one add; one that is partly present
+        splits; groups that reach the same count become one again."""
+        groups = self._groups
+        if self._owns_arena and len(groups) == 1 and all(m[0].grad is not None for m in groups[0][1]):
+            groups[0][0] += 1  # every parameter present on one count: nothing per parameter
+            return [[(0, self.ld, float(groups[0][0]))]] * self.K
+        live = [[] for _ in range(self.K)]
+        merged = {}  # count -> [its tensor, members]
+        for clock, members in groups:
+            here = [m for m in members if m[0].grad is not None]
+            if len(here) == len(members):
+                clock += 1
+                parts = [(clock, members)]
+            elif not here:
+                parts = [(clock, members)]
+            else:  # the present members go on with a count tensor of their own
+                parts = [(clock, [m for m in members if m[0].grad is None]), (clock + 1, here)]
+            if here:
+                t = float(parts[-1][0])
+                for _, k, o, n in here:
+                    live[k].append((o, n, t))
+            for c, ms in parts:
+                into = merged.setdefault(float(c), [c, []])
+                into[1].extend(ms)
+                if into[0] is not clock:
+                    for m in ms:
+                        self.state[m[0]]["step"] = into[0]
+        self._groups = list(merged.values())
+        return self._join([sorted(spans) for spans in live])
+
+    def _hp(self, t):
+        """The launch scalars of a step at count t (torch's _single_tensor_adam)."""
+        return adam_scalars(self.param_groups[0], t)
+
+
+class ArenaAdam(_AdamCounts, _ArenaOptimizer):
     """Adam/AdamW over one node's ParamArena, or over a ReplicaArena (K nodes of
     one process, [K, ld] parameter/gradient sets: one launch for all of them,
     each replica clipped by its own gradient norm)."""
@@ -269,13 +346,7 @@ class ArenaAdam(_ArenaOptimizer):
         # placement) each in its own candidate buffer, when _M / _V are None
         self._Mr, self._Vr = list(self._M.unbind(0)), list(self._V.unbind(0))
         self.exp_avg, self.exp_avg_sq = self._M.view(-1), self._V.view(-1)  # flat views (single-arena users)
-        # the step counts: [count tensor, [(param, replica, offset, numel)]] per group of parameters that
-        # share a count -- state[p]["step"] of its members IS the group's tensor, so a step advances a
-        # group with one add.  One group while every parameter has had a gradient on every step.
-        self._groups = [[torch.tensor(0.0), []]]
-        for p in self.param_groups[0]["params"]:
-            self._groups[0][1].append((p, *self._where[id(p)]))
-            self._bind_state(p)
+        self._start_counts()
         self._placed = None  # the candidate buffer holding M and V once _place chose one
         self._placed_for = None  # (P, G) data pointers the moments were placed against
         self._placements = 0  # searches run (a relocated P / G set is searched again)
@@ -298,14 +369,6 @@ class ArenaAdam(_ArenaOptimizer):
         self.state[p] = {"step": step, "exp_avg": self._Mr[k][o:o + n].view(p.shape),
                          "exp_avg_sq": self._Vr[k][o:o + n].view(p.shape)}
 
-    def state_dict(self):
-        """torch's layout, every parameter with a `step` tensor of its own (here
-        the parameters of a group share one; torch's optimizers, which advance
-        each entry in place, must not)."""
-        sd = super().state_dict()
-        sd["state"] = {i: {**st, "step": st["step"].clone()} for i, st in sd["state"].items()}
-        return sd
-
     def load_state_dict(self, state_dict):
         """torch's Optimizer.load_state_dict, then the loaded per-parameter
         moments are copied into the flat state buffers the kernel reads and the
@@ -324,15 +387,7 @@ class ArenaAdam(_ArenaOptimizer):
                     self._Mr[k][o:o + n].copy_(st["exp_avg"].reshape(-1))
                     self._Vr[k][o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
                 steps[id(p)] = float(st["step"]) if "step" in st else 0.0
-        groups = {}  # one group, and one count tensor, per distinct count
-        for k, sp in enumerate(self._spans):
-            for p, o, n in sp:
-                t = steps[id(p)]
-                g = groups.get(t) or groups.setdefault(t, [torch.tensor(t), []])
-                g[1].append((p, k, o, n))
-                self.state[p]["step"] = g[0]
-                self._bind_state(p)
-        self._groups = list(groups.values())
+        self._regroup(steps)
 
     def _place(self):
         """Choose the physical memory of the moments, once, before the first
@@ -432,50 +487,104 @@ class ArenaAdam(_ArenaOptimizer):
         else:
             ops.adam_step(self.P[k, a:b], self.G[k, a:b], self._Mr[k][a:b], self._Vr[k][a:b], clip_coef=clip, **hp)
 
-    def _ranges(self):
-        """Advance the count of every parameter that has a gradient now and
-        return, per replica, [(a, b, t)]: the contiguous ranges of present
-        parameters that share the count t (_join).  A group whose members
-        are all present advances with one add; one that is partly present
-        splits; groups that reach the same count become one again."""
-        groups = self._groups
-        if self._owns_arena and len(groups) == 1 and all(m[0].grad is not None for m in groups[0][1]):
-            groups[0][0] += 1  # every parameter present on one count: nothing per parameter
-            return [[(0, self.ld, float(groups[0][0]))]] * self.K
-        live = [[] for _ in range(self.K)]
-        merged = {}  # count -> [its tensor, members]
-        for clock, members in groups:
-            here = [m for m in members if m[0].grad is not None]
-            if len(here) == len(members):
-                clock += 1
-                parts = [(clock, members)]
-            elif not here:
-                parts = [(clock, members)]
-            else:  # the present members go on with a count tensor of their own
-                parts = [(clock, [m for m in members if m[0].grad is None]), (clock + 1, here)]
-            if here:
-                t = float(parts[-1][0])
-                for _, k, o, n in here:
-                    live[k].append((o, n, t))
-            for c, ms in parts:
-                into = merged.setdefault(float(c), [c, []])
-                into[1].extend(ms)
-                if into[0] is not clock:
-                    for m in ms:
-                        self.state[m[0]]["step"] = into[0]
-        self._groups = list(merged.values())
-        return self._join([sorted(spans) for spans in live])
 
-    def _hp(self, t):
-        """The launch scalars of a step at count t (torch's _single_tensor_adam)."""
-        g = self.param_groups[0]
-        lr, (b1, b2), eps, wd = float(g["lr"]), g["betas"], float(g["eps"]), float(g["weight_decay"])
-        decoupled = g["decoupled_weight_decay"]
-        bc1 = 1 - b1 ** t
-        bc2 = 1 - b2 ** t
-        return dict(lerp_w=1 - b1, beta2=b2, one_m_beta2=1 - b2, eps=eps,
-                    wd_factor=(1 - lr * wd) if (decoupled and wd != 0) else 1.0,
-                    l2_wd=wd if (not decoupled and wd != 0) else 0.0, step_size=-(lr / bc1), bc2_sqrt=math.sqrt(bc2))
+def fusable_adam8(spec_cls, kwargs, arena):
+    """True when OptimSpec(spec_cls, **kwargs) can run as ArenaAdam8bit on this arena:
+    AdamW8bit on an fp32 arena with a gradient set, a float learning rate."""
+    if spec_cls is not AdamW8bit or not _fp32_arena(arena):
+        return False
+    kw = dict(kwargs or {})
+    return not set(kw) - set(_ADAM8_KW) and not isinstance(kw.get("lr", 1e-3), torch.Tensor)
+
+
+_ADAM8_KW = ("lr", "betas", "eps", "weight_decay")
+
+
+class ArenaAdam8bit(_AdamCounts, _ArenaOptimizer):
+    """AdamW8bit (gym_amd.strategy.optim: AdamW with block-wise 8-bit moments) over one
+    node's ParamArena or a ReplicaArena: step() is one ga_adam8_step launch over the
+    [K, ld] sets and, with clipping, one ga_grad_clip_coef.  Counts, absent parameters
+    and launch ranges as ArenaAdam's (_AdamCounts); not an ArenaAdam, so nothing that
+    reaches for fp32 moments mistakes it for one.
+
+    The moments are two uint8 [K, ld] code sets and two fp32 [K, ld / 64] scale sets: 2.125
+    bytes per arena element and replica where ArenaAdam has 8.  Arena tensors start at
+    multiples of 64 elements and the padding between them is zero, so a block never holds
+    two tensors and a launch range, its end rounded up to a block, only takes the last
+    tensor's own padding along, which stays zero under the update.  state[p] holds
+    `step` and, as views of the flat sets, AdamW8bit's exp_avg_code / exp_avg_absmax /
+    exp_avg_sq_code / exp_avg_sq_absmax over the tensor's whole blocks, so state_dict() has
+    AdamW8bit's layout; load_state_dict() takes either class's dict, or a
+    torch.optim.AdamW / Adam / ArenaAdam dict, whose fp32 moments are quantised by
+    ga_adam8_encode."""
+
+    def __init__(self, params, arena, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, placement=True):
+        defaults = AdamW8bit([torch.zeros(1)], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay).defaults
+        super().__init__(params, defaults, arena)
+        if self.ld % ADAM8_BLOCK or any(o % ADAM8_BLOCK for sp in self._spans for _, o, _ in sp):
+            raise ValueError("ArenaAdam8bit: arena tensors must start at multiples of 64 elements")
+        dev, nb = self.P.device, self.ld // ADAM8_BLOCK
+        self._Mc = torch.full((self.K, self.ld), 127, dtype=torch.uint8, device=dev)  # the signed row's zero
+        self._Vc = torch.zeros(self.K, self.ld, dtype=torch.uint8, device=dev)
+        self._Ma = torch.zeros(self.K, nb, dtype=torch.float32, device=dev)
+        self._Va = torch.zeros(self.K, nb, dtype=torch.float32, device=dev)
+        self._start_counts()
+        self.placement = {"placed": False, "why": "no search for 8-bit AdamW"}
+
+    def state_bytes(self):
+        return sum(t.numel() * t.element_size() for t in (self._Mc, self._Vc, self._Ma, self._Va))
+
+    def _bind_state(self, p):
+        k, o, n = self._where[id(p)]
+        st = self.state.get(p)
+        a, b = o // ADAM8_BLOCK, (o + n + ADAM8_BLOCK - 1) // ADAM8_BLOCK  # the tensor's whole blocks
+        self.state[p] = {"step": st["step"] if st else self._groups[0][0],
+                         "exp_avg_code": self._Mc[k, a * ADAM8_BLOCK:b * ADAM8_BLOCK], "exp_avg_absmax": self._Ma[k, a:b],
+                         "exp_avg_sq_code": self._Vc[k, a * ADAM8_BLOCK:b * ADAM8_BLOCK],
+                         "exp_avg_sq_absmax": self._Va[k, a:b]}
+
+    def load_state_dict(self, state_dict):
+        """torch's Optimizer.load_state_dict, then the loaded moments go into the flat
+        sets and the state is re-pointed at their views: codes and scales are copied,
+        fp32 exp_avg / exp_avg_sq (a torch.optim.AdamW or ArenaAdam dict) are quantised
+        row by row with ga_adam8_encode.  A parameter without an entry starts at step 0
+        with zero moments."""
+        super().load_state_dict(state_dict)
+        loaded = {id(p): dict(self.state.get(p, {})) for p in self.param_groups[0]["params"]}
+        with torch.no_grad():
+            self._Mc.fill_(127)
+            for t in (self._Vc, self._Ma, self._Va):
+                t.zero_()
+            for k, sp in enumerate(self._spans):
+                full = [(o, n, loaded[id(p)]) for p, o, n in sp if "exp_avg" in loaded[id(p)]]
+                if full:  # encode the row's fp32 moments, then keep only these tensors' blocks
+                    rows = torch.zeros(2, self.ld, dtype=torch.float32, device=self.P.device)
+                    for o, n, st in full:
+                        rows[0, o:o + n].copy_(st["exp_avg"].reshape(-1))
+                        rows[1, o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
+                    ops.adam8_encode(rows[0], self._Mc[k], self._Ma[k], 0)
+                    ops.adam8_encode(rows[1], self._Vc[k], self._Va[k], 1)
+                for p, o, n in sp:
+                    st = loaded[id(p)]
+                    self.state[p] = {"step": None}
+                    self._bind_state(p)
+                    for key in ("exp_avg_code", "exp_avg_absmax", "exp_avg_sq_code", "exp_avg_sq_absmax"):
+                        if key in st:
+                            self.state[p][key].copy_(st[key].reshape(-1))
+        self._regroup({i: float(st["step"]) if "step" in st else 0.0 for i, st in loaded.items()})
+
+    def _prepare(self):
+        self._hps = {}  # the launch scalars per count of this step
+
+    def _launch(self, k, a, b, t, clip):
+        hp = self._hps.get(t) or self._hps.setdefault(t, self._hp(t))
+        if k is None:
+            ops.adam8_step(self.P, self.G, self._Mc, self._Ma, self._Vc, self._Va, clip_coef=clip, **hp)
+            return
+        b = (b + ADAM8_BLOCK - 1) // ADAM8_BLOCK * ADAM8_BLOCK  # the last tensor's own zero padding
+        ba, bb = a // ADAM8_BLOCK, b // ADAM8_BLOCK
+        ops.adam8_step(self.P[k, a:b], self.G[k, a:b], self._Mc[k, a:b], self._Ma[k, ba:bb], self._Vc[k, a:b],
+                       self._Va[k, ba:bb], clip_coef=clip, **hp)
 
 
 _SGD_KW = ("lr", "momentum", "dampening", "weight_decay", "nesterov")
@@ -1130,13 +1239,13 @@ class ArenaAdafactor(_ArenaOptimizer):
         return loss
 
 
-FUSED = (ArenaAdam, ArenaSGD, ArenaMuon, ArenaAdafactor)  # the inner optimizers whose step(max_norm=) clips on the device
+FUSED = (ArenaAdam, ArenaAdam8bit, ArenaSGD, ArenaMuon, ArenaAdafactor)  # the inner optimizers whose step(max_norm=) clips on the device
 
 
 def build_fused(spec, params, arena, placement=True, models=None):
     """The fused inner optimizer of OptimSpec `spec` over `arena` (ArenaAdam for
     torch's AdamW / Adam, ArenaSGD for torch's SGD, ArenaAdafactor for torch's
-    Adafactor under ADAFACTOR_FUSED_DEFAULT, ArenaMuon for MuonAdamW with
+    Adafactor under ADAFACTOR_FUSED_DEFAULT, ArenaAdam8bit for AdamW8bit, ArenaMuon for MuonAdamW with
     `fused=True` -- MUON_FUSED_DEFAULT without the kwarg), or None when the spec
     stays on torch: another optimizer or option, a bf16 arena, or
     GA_FUSED_OPTIM=0.  models: the arena's modules (one per replica), from which
@@ -1173,4 +1282,7 @@ def build_fused(spec, params, arena, placement=True, models=None):
     if ADAFACTOR_FUSED_DEFAULT and fusable_adafactor(spec.cls, kw, arena) and hasattr(ops, "adafactor_stats"):
         return ArenaAdafactor(params, arena, placement=placement,
                               **{k: v for k, v in kw.items() if k in _ADAFACTOR_KW})
+    # and one written before ga_adam8_step keeps the unfused AdamW8bit
+    if fusable_adam8(spec.cls, kw, arena) and hasattr(ops, "adam8_step"):
+        return ArenaAdam8bit(params, arena, placement=placement, **kw)
     return None

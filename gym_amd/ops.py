@@ -1085,6 +1085,81 @@ def sgd_step(param, grad, buf, *, neg_lr, momentum, one_m_dampening, weight_deca
                             int(bool(nesterov)), int(bool(first)), _p(clip_coef), _stream()), "ga_sgd_step")
 
 
+ADAM8_BLOCK = 64  # elements under one scale of the 8-bit moments (ga_adam8_step)
+_adam8_cache = {}
+
+
+def adam8_tables(device=None):
+    """The code books of the 8-bit AdamW moments, fp32 (codes[2, 256], thresholds[2, 256]):
+    row 0 signed (exp_avg), row 1 unsigned (exp_avg_sq).  The only definition of the
+    tables: the kernel receives them as device pointers, AdamW8bit and the tests call
+    this.  The "dynamic" code book of Dettmers et al.: for decade i = 0..6, F = 2^i
+    (signed) or 2^(i+1) (unsigned) values 10^(i-6) * the midpoints of linspace(0.1, 1,
+    F + 1), the signed row also their negatives, plus 0 and 1, sorted (float64, rounded
+    to fp32 once).  thresholds[r, j] is the fp32 midpoint of codes j and j + 1; entry
+    255 is unused (+inf).  A value x in [-1, 1] has the code `number of thresholds < x`.
+    Cached per device."""
+    key = str(device)
+    if key not in _adam8_cache:
+        import numpy as np
+        rows = []
+        for signed in (True, False):
+            vals = [0.0, 1.0]
+            for i in range(7):
+                b = np.linspace(0.1, 1.0, 2 ** (i if signed else i + 1) + 1)
+                mid = 10.0 ** (i - 6) * (b[:-1] + b[1:]) / 2
+                vals += list(mid) + (list(-mid) if signed else [])
+            rows.append(np.sort(np.asarray(vals, np.float64)).astype(np.float32))
+        codes = np.stack(rows)
+        assert codes.shape == (2, 256)
+        thr = np.full((2, 256), np.inf, np.float32)
+        thr[:, :255] = ((codes[:, :-1].astype(np.float64) + codes[:, 1:].astype(np.float64)) / 2).astype(np.float32)
+        _adam8_cache[key] = (torch.from_numpy(codes).to(device), torch.from_numpy(thr).to(device))
+    return _adam8_cache[key]
+
+
+def _adam8_state(who, code, absmax, like, K, ld):
+    """A moment of ga_adam8_step: uint8 codes laid out as `like` (the parameter set) and
+    one fp32 scale per 64 of them."""
+    c2, a2 = _as2d(code), _as2d(absmax)
+    if (c2.dtype != torch.uint8 or c2.shape != like.shape or c2.stride(-1) != 1 or a2.dtype != torch.float32
+            or a2.shape != (K, like.shape[1] // ADAM8_BLOCK) or a2.stride(-1) != 1):
+        raise ValueError(f"{who}: a moment is uint8 codes [K, n] and fp32 scales [K, n / 64]")
+    if K > 1 and (c2.stride(0) != ld or a2.stride(0) * ADAM8_BLOCK != ld):
+        raise ValueError(f"{who}: code rows must be ld apart and scale rows ld / 64")
+    return c2, a2
+
+
+def adam8_step(param, grad, exp_avg_code, exp_avg_absmax, exp_avg_sq_code, exp_avg_sq_absmax, lerp_w, beta2,
+               one_m_beta2, eps, wd_factor, l2_wd, step_size, bc2_sqrt, clip_coef=None):
+    """One fused 8-bit AdamW / Adam step over fp32 [K, ld] replica sets (or 1-D buffers) of
+    whole 64-element blocks, the moments as uint8 codes and fp32 block scales (see
+    include/gym_amd.h)."""
+    ts, K, ld = _one_layout((param, grad), clip_coef, "adam8_step: param/grad must be fp32 replica sets of one layout")
+    n = ts[0].shape[1]
+    mc, ma = _adam8_state("adam8_step", exp_avg_code, exp_avg_absmax, ts[0], K, ld)
+    vc, va = _adam8_state("adam8_step", exp_avg_sq_code, exp_avg_sq_absmax, ts[0], K, ld)
+    _gpu(mc, ma, vc, va)
+    if clip_coef is not None and clip_coef.numel() < 2 * K:
+        raise ValueError("adam8_step: clip_coef must hold 2 floats per replica")
+    codes, thr = adam8_tables(ts[0].device)
+    check(lib().ga_adam8_step(_GA_F32, _p(ts[0]), _p(ts[1]), _p(mc), _p(ma), _p(vc), _p(va), K, ld, n, _p(codes),
+                              _p(thr), float(lerp_w), float(beta2), float(one_m_beta2), float(eps), float(wd_factor),
+                              float(l2_wd), float(step_size), float(bc2_sqrt), _p(clip_coef), _stream()),
+          "ga_adam8_step")
+
+
+def adam8_encode(x, code, absmax, row):
+    """Quantise the fp32 [K, ld] set (or 1-D buffer) x of whole 64-element blocks into
+    ga_adam8_step's codes and block scales with table row `row` (0 signed, 1 unsigned)."""
+    ts, K, ld = _one_layout((x,), None, "adam8_encode: x must be an fp32 replica set")
+    c2, a2 = _adam8_state("adam8_encode", code, absmax, ts[0], K, ld)
+    _gpu(c2, a2)
+    _, thr = adam8_tables(ts[0].device)
+    check(lib().ga_adam8_encode(_p(ts[0]), _p(c2), _p(a2), K, ld, ts[0].shape[1], int(row), _p(thr), _stream()),
+          "ga_adam8_encode")
+
+
 MUON_GRAM, MUON_POLY, MUON_UPDATE = 0, 1, 2  # ga_muon_gemm's kinds
 MUON_PREP_TILE = 64  # edge of a prepare / apply job tile
 

@@ -947,6 +947,39 @@ GA_API int ga_sgd_step(int dtype, void* param, void* grad, float* momentum_buf, 
                        float neg_lr, float momentum, float one_m_dampening, float weight_decay, int nesterov,
                        int first, const float* clip_coef, hipStream_t stream);
 
+/*
+ * One fused 8-bit AdamW / Adam step (block-wise quantised moments: Dettmers et al., "8-bit
+ * Optimizers via Block-wise Quantization") over K replicas of an fp32 arena.  Each moment is
+ * a uint8 [K, ld] set of codes and an fp32 [K, ld / 64] set of scales, one per block of 64
+ * consecutive elements; `codes` and `thresholds` are the fp32 [2, 256] tables of
+ * gym_amd.ops.adam8_tables (row 0 signed, for exp_avg; row 1 unsigned, for exp_avg_sq; 255
+ * thresholds of a row are used), in device memory.  Per block, all in fp32:
+ *   m = codes[0][exp_avg_code] * exp_avg_absmax,  v = codes[1][exp_avg_sq_code] * exp_avg_sq_absmax
+ *   g = grad * clip_coef[2k]  (and written back) under ga_adam_step's rule
+ *   ga_adam_step's element update of (p, g, m, v) with the eight scalars (p from the fp32 m, v)
+ *   absmax = max |x| over the block; code = the number of thresholds < x / absmax (0 when
+ *   absmax == 0; IEEE division); for exp_avg_sq a value > 0 is never stored as code 0
+ * Fresh state: exp_avg_code 127, exp_avg_sq_code 0, scales 0.  n and ld are multiples of 64
+ * (a launch range starts and ends on block boundaries; the arena's padding is zero and stays
+ * zero), param and grad 16-byte aligned, the other arrays 4-byte aligned.  Bytes per element:
+ * 16.25 (+4 when the clipped gradient is written back).
+ * No reference counterpart (the reference builds torch optimizers by class): the "adamw8bit"
+ * spec, gym_amd.strategy.optim.AdamW8bit.
+ */
+GA_API int ga_adam8_step(int dtype, void* param, void* grad, uint8_t* exp_avg_code, float* exp_avg_absmax,
+                         uint8_t* exp_avg_sq_code, float* exp_avg_sq_absmax, int64_t K, int64_t ld, int64_t n,
+                         const float* codes, const float* thresholds, float lerp_w, float beta2, float one_m_beta2,
+                         float eps, float wd_factor, float l2_wd, float step_size, float bc2_sqrt,
+                         const float* clip_coef, hipStream_t stream);
+
+/*
+ * Quantise an fp32 [K, ld] set (n elements per replica, n and ld multiples of 64, x 16-byte
+ * aligned) into ga_adam8_step's codes and scales with table row `row` (0 signed, 1 unsigned)
+ * of `thresholds` [2, 256]: the encode half of the step, for loading fp32 moments.
+ */
+GA_API int ga_adam8_encode(const float* x, uint8_t* code, float* absmax, int64_t K, int64_t ld, int64_t n, int row,
+                           const float* thresholds, hipStream_t stream);
+
 /* ---- Muon inner step: batched Newton-Schulz on the bf16 MFMA ------------- */
 
 /*
